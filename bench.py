@@ -8,6 +8,12 @@ With --gpus N (launched by torch.distributed.run) every rank trains its own
 128 learners [rank*128, (rank+1)*128) of the same ensemble on its own GPU: weak
 scaling, no collective on the data path (learners are independent).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps and prints the headline.  --dump-outputs DIR
+also writes the forest of the last timed step as .npy files, so that two builds can be
+compared output for output (same arguments, same inputs).  --full adds every other
+figure (roofline, breakdown_ms, sampler, non-dyadic labels, continuous features, CPU
+baseline, build record); each takes fits of its own after the timed steps.
 """
 import argparse
 import json
@@ -109,6 +115,14 @@ def parse():
     ap.add_argument("--bins", type=int, default=32)
     ap.add_argument("--partitions", type=int, default=128)
     ap.add_argument("--seed", type=int, default=20261015)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the forest the last timed step returned "
+                         "as DIR/<name>.npy (float64/float32, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else this benchmark reports: "
+                         "the serialized fit behind roofline / breakdown_ms, the sampler at nproc "
+                         "partitions, the non-dyadic and continuous-feature fits, the CPU "
+                         "baseline and the build record (the options below apply to these)")
     ap.add_argument("--sampler-partitions", type=int, default=None,
                     help="also time one fit's sampler at this P (default: nproc)")
     ap.add_argument("--cpu-rows", type=int, default=1_000_000)
@@ -121,6 +135,8 @@ def parse():
                     help="skip the extra timing of the C3 shape on continuous features")
     ap.add_argument("--continuous-steps", type=int, default=3)
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     w = WORKLOADS[a.workload]
     for k in ("rows", "features", "learners", "depth"):
         if getattr(a, k) is None:
@@ -286,6 +302,53 @@ def build_record():
     return rec
 
 
+DUMP_BUDGET = 64 * 1000 * 1000  # bytes, all --dump-outputs files together
+NODE_FIELDS = ("id", "left", "right", "feature", "split_bin", "threshold", "prediction",
+               "impurity", "gain")
+
+
+def dump_outputs(forest, num_features, outdir):
+    """Write what nat.fit returned in the last timed step, as a caller reads it back
+    (NativeForest.tree / .subspace), into float64 / float32 .npy files:
+      nodes.npy        [nodes of all trees, 1 + 9] fp64: tree index, then NODE_FIELDS (pre-order)
+      tree_offsets.npy [trees + 1] fp64: first row of each tree in nodes.npy / stats.npy
+      stats.npy        [nodes of all trees, stats per node] fp64 impurity statistics
+      stats_rows.npy   [rows kept] fp64: the rows of the full stats array that stats.npy holds
+      subspace.npy     [trees, features] fp32: 1 where the tree's subspace has the feature
+    stats.npy is the one array that can outgrow the budget (deep gini trees of many
+    classes); then it keeps a fixed, seeded sample of its rows."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    T = len(forest)
+    nodes, stats, sub = [], [], np.zeros((T, num_features), np.float32)
+    for t in range(T):
+        nd, st = forest.tree(t)
+        a = np.empty((len(nd), 1 + len(NODE_FIELDS)), np.float64)
+        a[:, 0] = t
+        for k, name in enumerate(NODE_FIELDS):
+            a[:, 1 + k] = nd[name]
+        nodes.append(a)
+        stats.append(st)
+        sub[t, forest.subspace(t)] = 1.0
+    offsets = np.concatenate([[0], np.cumsum([len(a) for a in nodes])]).astype(np.float64)
+    nodes = np.concatenate(nodes)
+    width = max(s.shape[1] for s in stats)
+    full = np.zeros((len(nodes), width), np.float64)
+    full[:, :] = np.nan
+    for t, s in enumerate(stats):
+        full[int(offsets[t]):int(offsets[t + 1]), : s.shape[1]] = s
+    rows = np.arange(len(nodes))
+    left = DUMP_BUDGET - nodes.nbytes - offsets.nbytes - sub.nbytes - 1024 * 8  # .npy headers
+    keep = max(1, left // (8 * (width + 1)))
+    if keep < len(rows):
+        rows = np.sort(np.random.default_rng(20261019).choice(len(rows), size=keep, replace=False))
+    arrays = {"nodes": nodes, "tree_offsets": offsets, "stats": full[rows],
+              "stats_rows": rows.astype(np.float64), "subspace": sub}
+    for name, arr in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), arr)
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -348,10 +411,14 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     timings = []
-    for _ in range(args.steps):
+    last = None  # the last timed step's forest, kept for --dump-outputs
+    for i in range(args.steps):
         f = step()
         timings.append(f.timing())
-        f.free()
+        if args.dump_outputs and rank == 0 and i == args.steps - 1:
+            last = f
+        else:
+            f.free()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -362,7 +429,43 @@ def main():
         elapsed = float(t.item())
     ms_per_step = 1000.0 * elapsed / args.steps
     value = world * L * N * args.steps / elapsed
+    if last is not None:
+        dump_outputs(last, F, args.dump_outputs)
+        last.free()
+    out = {
+        "metric": "estimator×rows trained/sec", "value": round(value, 1),
+        "unit": "estimator*rows/s", "n_gpus": world, "backend": args.backend if world > 1 else None,
+        "devices_used": min(world, torch.cuda.device_count()), "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "int64",
+        "data": "synthetic (device generator k_synth: splitmix64 codes mod 32, "
+                + ("class labels)" if cls else "dyadic labels)"),
+        "config": {"workload": args.workload_name,
+                   "rows": N, "features": F, "learners_per_gpu": L, "learners_total": L * world,
+                   "max_depth": args.depth, "max_bins": args.bins, "partitions": args.partitions,
+                   "classes": args.classes, "replacement": args.replacement,
+                   "sample_ratio": args.ratio, "parallelism": f"learner-shard x{world}"},
+        "replication": replication,
+        "value_incl_replication": (round(world * L * N * args.steps / (elapsed + replication["seconds"]), 1)
+                                   if replication else None),
+        "full": args.full,
+    }
+    if args.full:
+        out.update(full_report(args, nat, ctx, ds, step, world, rank, lb, part))
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    ctx.close()
+    if world > 1:
+        dist.destroy_process_group()
 
+
+def full_report(args, nat, ctx, ds, step, world, rank, lb, part):
+    """Everything the benchmark reports beside the headline (--full); each part takes fits
+    of its own, after the timed steps.  Returns the keys to add to the result line."""
+    import torch
+
+    N, F, L = args.rows, args.features, args.learners
+    cls = args.classes > 0
     # Kernel-level figures (roofline, breakdown) come from one more fit with the learner
     # halves serialized (SBAG_OVERLAP=0).  In the timed steps the two halves of the learner
     # range run on two streams (sbag_fit, DESIGN.md §7) and each kernel shares the GPU with
@@ -491,22 +594,8 @@ def main():
         ds.free()
         continuous = continuous_fit(nat, ctx, N, F, L, args.depth, args.bins, part, steps=args.continuous_steps)
     out = {
-        "metric": "estimator×rows trained/sec", "value": round(value, 1),
-        "unit": "estimator*rows/s", "n_gpus": world, "backend": args.backend if world > 1 else None,
-        "devices_used": min(world, torch.cuda.device_count()), "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "int64",
-        "data": "synthetic (device generator k_synth: splitmix64 codes mod 32, "
-                + ("class labels)" if cls else "dyadic labels)"),
-        "config": {"workload": args.workload_name,
-                   "rows": N, "features": F, "learners_per_gpu": L, "learners_total": L * world,
-                   "max_depth": args.depth, "max_bins": args.bins, "partitions": args.partitions,
-                   "classes": args.classes, "replacement": args.replacement,
-                   "sample_ratio": args.ratio, "parallelism": f"learner-shard x{world}"},
         "roofline": roofline, "breakdown_ms": breakdown, "sampler_at_nproc_partitions": sampler_p,
-        "nondyadic_labels": nondyadic, "continuous_features": continuous, "replication": replication,
-        "value_incl_replication": (round(world * L * N * args.steps / (elapsed + replication["seconds"]), 1)
-                                   if replication else None),
+        "nondyadic_labels": nondyadic, "continuous_features": continuous,
         "kernel_timing": "roofline and breakdown_ms: a fit after the timed steps with the learner "
                          "halves serialized (SBAG_OVERLAP=0, after one such warm fit), so each "
                          "launch runs alone; the timed steps overlap the two halves on two streams",
@@ -514,11 +603,7 @@ def main():
     }
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    ctx.close()
-    if world > 1:
-        dist.destroy_process_group()
+    return out
 
 
 if __name__ == "__main__":

@@ -13,7 +13,7 @@ fi
 for v in "$@"; do
   n=$(echo "$v" | tr '= ' '__')
   e=$v; [ "$v" = "none" ] && e=""
-  env $e timeout -k 10 300 python3 bench.py --workload $W --steps 3 --warmup 1 --no-cpu-baseline --sampler-partitions 128 > $OUT/bench_${W}_$n.log 2>&1 || { echo "bench $W $v failed rc=$?"; tail -5 $OUT/bench_${W}_$n.log; exit 1; }
+  env $e timeout -k 10 300 python3 bench.py --full --workload $W --steps 3 --warmup 1 --no-cpu-baseline --sampler-partitions 128 > $OUT/bench_${W}_$n.log 2>&1 || { echo "bench $W $v failed rc=$?"; tail -5 $OUT/bench_${W}_$n.log; exit 1; }
   python3 -c "import json;d=json.loads([l for l in open('$OUT/bench_${W}_$n.log') if l.startswith('{')][-1]);b=d['breakdown_ms'];print('$W $n step', d['ms_per_step'], 'hist', b['hist_ms'], 'part', b['partition_ms'], 'split', b['split_ms'], 'sample', b['sample_ms'])"
 done
 echo "ab $TAG done"

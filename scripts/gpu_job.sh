@@ -6,8 +6,8 @@
 #   steps:
 #     tests[=<pytest args>]   GPU suite (default: the whole -m gpu suite)
 #     smoke                   __graft_entry__.smoke()
-#     bench                   default `python bench.py` (the driver's line)
-#     c3 | c4 | c5            bench.py --workload <w>, short (env passes through, e.g. SBAG_*)
+#     bench                   `python bench.py --full` (the headline and every other figure)
+#     c3 | c4 | c5            bench.py --full --workload <w>, short (env passes through, e.g. SBAG_*)
 #     c4nd                    the C4 shard with real-valued labels (bench.py's nondyadic line)
 #     cont                    scripts/bench_continuous.py (C3 shape on continuous features)
 #     gbm                     scripts/bench_gbm.py
@@ -48,21 +48,21 @@ run_step() {
       timeout -k 10 200 python3 -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke$tag.log" 2>&1
       rc=$?; tail -2 "$OUT/smoke$tag.log"; return $rc ;;
     bench)
-      timeout -k 10 500 python3 bench.py > "$OUT/bench$tag.log" 2>&1
+      timeout -k 10 500 python3 bench.py --full > "$OUT/bench$tag.log" 2>&1
       rc=$?; [ $rc -ne 0 ] && tail -20 "$OUT/bench$tag.log"; summ "$OUT/bench$tag.log"; return $rc ;;
     c3|c4|c5)
       local extra="--steps 3 --warmup 1"
       [ "$st" = c4 ] && extra="--steps 2 --warmup 1"
-      timeout -k 10 400 python3 bench.py --workload $st $extra --no-cpu-baseline --no-nondyadic --no-continuous \
+      timeout -k 10 400 python3 bench.py --full --workload $st $extra --no-cpu-baseline --no-nondyadic --no-continuous \
         > "$OUT/bench_$st$tag.log" 2>&1
       rc=$?; [ $rc -ne 0 ] && tail -20 "$OUT/bench_$st$tag.log"; summ "$OUT/bench_$st$tag.log"; return $rc ;;
     c4nd)
       # the C4 shard with real-valued labels (bench.py's nondyadic line on the c4 workload)
-      timeout -k 10 500 python3 bench.py --workload c4 --steps 1 --warmup 1 --no-cpu-baseline --no-continuous \
+      timeout -k 10 500 python3 bench.py --full --workload c4 --steps 1 --warmup 1 --no-cpu-baseline --no-continuous \
         --nondyadic-steps 2 > "$OUT/bench_c4nd$tag.log" 2>&1
       rc=$?; [ $rc -ne 0 ] && tail -20 "$OUT/bench_c4nd$tag.log"; summ "$OUT/bench_c4nd$tag.log"; return $rc ;;
     nondyadic)
-      timeout -k 10 400 python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-continuous --nondyadic-steps 3 \
+      timeout -k 10 400 python3 bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-continuous --nondyadic-steps 3 \
         > "$OUT/bench_nd$tag.log" 2>&1
       rc=$?; [ $rc -ne 0 ] && tail -20 "$OUT/bench_nd$tag.log"; summ "$OUT/bench_nd$tag.log"; return $rc ;;
     cont)
@@ -107,7 +107,7 @@ run_step() {
       local w=${st#trace_} d="$OUT/trace_${st#trace_}$tag"
       mkdir -p "$d"
       SBAG_OVERLAP=0 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$d" -o trace -- \
-        python3 bench.py --workload $w --steps 1 --warmup 1 --no-cpu-baseline --no-nondyadic --no-continuous > "$d/trace.log" 2>&1
+        python3 bench.py --full --workload $w --steps 1 --warmup 1 --no-cpu-baseline --no-nondyadic --no-continuous > "$d/trace.log" 2>&1
       rc=$?; [ $rc -ne 0 ] && { tail -20 "$d/trace.log"; return $rc; }
       f=$(find "$d" -name "*kernel_stats.csv" | head -1); head -16 "$f" | cut -d, -f1-5 | cut -c1-160
       return 0 ;;

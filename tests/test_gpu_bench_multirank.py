@@ -35,7 +35,7 @@ def test_bench_two_ranks_gloo_one_gpu():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--rows", str(rows),
-           "--steps", "1", "--warmup", "1", "--sampler-partitions", "128"]
+           "--steps", "1", "--warmup", "1", "--full", "--sampler-partitions", "128"]
     env = dict(os.environ)
     env.setdefault("MASTER_ADDR", "127.0.0.1")
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
