@@ -235,6 +235,25 @@ int sbag_predict(sbag_ctx* ctx, const sbag_forest* f, const double* X, int64_t n
                  double* per_tree_out /* [trees x num_rows] or NULL */);
 int sbag_predict_dataset(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* ds, int32_t agg,
                          double* out /* [num_rows] */);
+/* Out-of-bag predictions of a fitted ensemble on its own training data.  `ds` is the
+   dataset the forest was fitted on, `sampler` and `partition_offsets` the fit's (the
+   learner range must hold as many learners as the forest has trees): the bags are
+   bfunctions.bag again (sbag_sample's counts; nothing is kept from the fit).  Row r is
+   out of bag for learner i iff counts[i][r] == 0; n_oob[r] counts those learners and
+   out[r] aggregates their trees only, in learner order:
+     SBAG_AGG_MEAN  s = 0.0; s = s + tree_i(row) for every out-of-bag i; out = s / n_oob
+                    (BaggingRegressor.scala:248-256 over the out-of-bag learners)
+     SBAG_AGG_MODE  breeze mode of the out-of-bag votes, the first class to reach the
+                    final maximum count (BaggingClassifier.scala:248-257)
+   and out[r] = NaN where n_oob[r] == 0 (every row when the bags are drawn without
+   replacement at ratio 1.0; not an error).  A Poisson draw above 255 fails as in a fit.
+   The learners go through the device in batches when their counts exceed the budget of a
+   fit's buffers; SBAG_AGG_MODE over several batches with more than 256 MB of carried
+   class counters (2 x classes x num_rows bytes) is SBAG_EUNSUPPORTED. */
+int sbag_predict_oob(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* ds,
+                     const sbag_sampler_params* sampler, const int64_t* partition_offsets,
+                     int32_t num_partitions, int32_t agg, double* out /* host [num_rows] */,
+                     int32_t* n_oob_out /* host [num_rows] or NULL */);
 /* ordered aggregation of per-learner predictions on the host:
    votes [num_learners x num_rows] fp64, learner order */
 int sbag_aggregate(sbag_ctx* ctx, const double* votes, int32_t num_learners, int64_t num_rows,

@@ -29,7 +29,7 @@ EXPORTED = [
     "sbag_fit", "sbag_fit_booster", "sbag_forest_num_trees", "sbag_forest_tree_info", "sbag_forest_subspace",
     "sbag_forest_nodes", "sbag_forest_create", "sbag_forest_free", "sbag_forest_timing",
     "sbag_predict", "sbag_predict_dataset", "sbag_aggregate", "sbag_predict_dataset_device",
-    "sbag_aggregate_device",
+    "sbag_aggregate_device", "sbag_predict_oob",
 ]
 
 
@@ -149,6 +149,7 @@ def lib():
             "sbag_aggregate": [P, P, i32, i64, i32, P],
             "sbag_predict_dataset_device": [P, P, P, i32, i32, P],
             "sbag_aggregate_device": [P, P, i32, i32, i64, i32, i32, i32, P],
+            "sbag_predict_oob": [P, P, P, ctypes.POINTER(SamplerParams), P, i32, i32, P, P],
         }
         for name, args in sig.items():
             fn = getattr(L, name)
@@ -507,6 +508,25 @@ def predict_dataset(ctx, forest, dataset, agg):
     out = np.zeros(dataset.shape[0], np.float64)
     check(lib().sbag_predict_dataset(ctx.handle, forest.handle, dataset.handle, agg, ptr(out)))
     return out
+
+
+def predict_oob(ctx, forest, dataset, *, replacement, sample_ratio, seed, learner_begin, learner_end,
+                partition_offsets=None, agg):
+    """Out-of-bag predictions (sbag_predict_oob) of `forest` on the dataset it was fitted
+    on, the sampler arguments and partition offsets being the fit's: (pred fp64 [N], NaN
+    where no learner left the row out; n_oob int32 [N])."""
+    p = SamplerParams(int(replacement), 0, float(sample_ratio), int(seed), learner_begin, learner_end)
+    off = None
+    P = 1
+    if partition_offsets is not None:
+        off = np.ascontiguousarray(partition_offsets, np.int64)
+        P = len(off) - 1
+    n = dataset.shape[0]
+    out = np.zeros(n, np.float64)
+    n_oob = np.zeros(n, np.int32)
+    check(lib().sbag_predict_oob(ctx.handle, forest.handle, dataset.handle, ctypes.byref(p), ptr(off),
+                                 P, agg, ptr(out), ptr(n_oob)))
+    return out, n_oob
 
 
 def aggregate(ctx, votes, agg):

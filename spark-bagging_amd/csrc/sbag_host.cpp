@@ -5247,6 +5247,120 @@ int sbag_predict_dataset_device(sbag_ctx* c, const sbag_forest* f, const sbag_da
   return SBAG_OK;
 }
 
+// Out-of-bag predictions: the bags of the fit are regenerated by the sampler (nothing is
+// kept from the fit) a learner batch at a time, and each batch goes through k_predict_oob
+// (the LDS-tiled plan) or, where plan_tiled refuses, through the per-tree predictions of
+// k_predict and k_aggregate_oob.  One batch when the counts (and the fallback's votes) fit
+// the budget a fit's per-replica buffers get; SBAG_OOB_BATCH_LEARNERS forces the batch size
+// (read on every call).
+int sbag_predict_oob(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds,
+                     const sbag_sampler_params* sp, const int64_t* partition_offsets, int32_t P,
+                     int32_t agg, double* out, int32_t* n_oob_out) {
+  if (!c || !f || !ds || !sp || !out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(check_sampler(sp));
+  TRY(check_agg(f, agg));
+  const int L = (int)f->trees.size();
+  if (sp->learner_end - sp->learner_begin != L)
+    return fail(SBAG_EINVAL, "the sampler's learner range holds " +
+                                 std::to_string(sp->learner_end - sp->learner_begin) +
+                                 " learners, the forest " + std::to_string(L) + " trees");
+  const int64_t N = ds->N;
+  if (partition_offsets && P >= 1 && partition_offsets[P] != N)
+    return fail(SBAG_EINVAL, "partition_offsets must end at the dataset's row count");
+  std::vector<int64_t> poff;
+  TRY(check_partitions(P, partition_offsets, N, poff));
+  for (const HTree& t : f->trees)
+    for (int32_t g : t.sub)
+      if (g >= ds->F) return fail(SBAG_EINVAL, "dataset has fewer features than the model");
+  if (ds->ctx->device != c->device)
+    return fail(SBAG_EINVAL, "dataset lives on device " + std::to_string(ds->ctx->device) +
+                                 ", the context on device " + std::to_string(c->device));
+  if (N == 0) return SBAG_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const int ncls = std::max(f->nclasses, 1);
+  PredictArgs pa{};
+  pa.code_bytes = ds->code_bytes;
+  pa.S = ds->S;
+  pa.N = N;
+  pa.agg = agg;
+  TiledPlan Pl;
+  const bool tiled = ds->code_bytes != 4 && plan_tiled(f, pa, ds->F, [&](int g, double thr) {
+    const std::vector<double>& d = ds->dict[g];
+    return (int64_t)(std::upper_bound(d.begin(), d.end(), thr) - d.begin()) - 1;
+  }, Pl);
+  // bytes per learner of a batch: its counts row, and the fallback's fp64 predictions
+  const double per = (double)N * (tiled ? 1.0 : 9.0);
+  int batch = (int)std::max(1.0, std::min((double)L, std::floor(bins_budget(c) / per)));
+  if (const char* e = getenv("SBAG_OOB_BATCH_LEARNERS")) batch = std::max(1, std::min(L, atoi(e)));
+  const bool several = batch < L;
+  const bool mode_agg = agg == SBAG_AGG_MODE;
+  // mode counters in global memory: carried between batches (u16 [classes][N]), and the
+  // fallback's own (one batch: row ranges of at most 256 MB, as mode_counters)
+  int64_t gcnt_rows = 0;
+  if (mode_agg && (several || !tiled)) {
+    const int64_t cap_rows = std::max<int64_t>(256, ((int64_t)256 << 20) / (2 * ncls));
+    if (several && N > cap_rows)
+      return fail(SBAG_EUNSUPPORTED,
+                  "out-of-bag mode over several learner batches needs " +
+                      std::to_string((int64_t)2 * ncls * N) + " bytes of carried class counters (limit 256 MB)");
+    gcnt_rows = std::min(N, cap_rows);
+  }
+  double* d_out;
+  int32_t *d_noob, *d_gmax = nullptr;
+  uint16_t* d_gcnt = nullptr;
+  uint8_t* d_counts;
+  double* d_votes = nullptr;
+  TRY(ws_typed(c, "pout", (size_t)N, &d_out));
+  TRY(ws_typed(c, "oob_n", (size_t)N, &d_noob));
+  if (mode_agg) TRY(ws_typed(c, "oob_max", (size_t)N, &d_gmax));
+  if (gcnt_rows) TRY(ws_typed(c, "mode_cnt", (size_t)ncls * gcnt_rows, &d_gcnt));
+  TRY(ws_typed(c, "counts", (size_t)batch * N, &d_counts));
+  const DevNode* f_nodes = nullptr;
+  const int64_t* f_off = nullptr;
+  if (tiled) {
+    TRY(upload_plan(c, Pl, pa));
+    pa.codes = ds->d_codes;
+    pa.out = d_out;
+  } else {
+    TRY(upload_forest(c, f, &f_nodes, &f_off));
+    TRY(ws_typed(c, "oob_votes", (size_t)batch * N, &d_votes));
+  }
+  for (int b0 = 0; b0 < L; b0 += batch) {
+    const int b1 = std::min(L, b0 + batch);
+    sbag_sampler_params sb = *sp;
+    sb.learner_begin = sp->learner_begin + b0;
+    sb.learner_end = sp->learner_begin + b1;
+    TRY(run_sampler(c, &sb, poff, N, d_counts, false));
+    if (tiled) {
+      OobArgs oa{};
+      oa.counts = d_counts;
+      oa.t0 = b0;
+      oa.t1 = b1;
+      oa.first = b0 == 0;
+      oa.last = b1 == L;
+      oa.n_oob = d_noob;
+      oa.gmax = d_gmax;
+      oa.gcnt = d_gcnt;
+      launch_predict_oob(c->stream, pa, oa);
+    } else {  // the batch's per-tree predictions by the global-memory walk, then the masked aggregation
+      launch_predict(c->stream, nullptr, ds->d_codes, ds->code_bytes, ds->d_dict, ds->d_dict_off, N, ds->F,
+                     ds->S, f_nodes, f_off + b0, b1 - b0, kAggVotes, ncls, nullptr, nullptr, d_votes, 8,
+                     nullptr, 0);
+      HIP_TRY(hipGetLastError());
+      launch_aggregate_oob(c->stream, d_votes, d_counts, b1 - b0, N, agg, ncls, d_out, d_noob, d_gmax,
+                           d_gcnt, gcnt_rows, b0 == 0, b1 == L);
+    }
+    HIP_TRY(hipGetLastError());
+    // (the Poisson overflow flag is rewritten by the next batch's sampler: read it now, with
+    // the batch's kernels already queued)
+    if (sp->replacement) TRY(sampler_overflow(c));
+  }
+  TRY(d2h(c, out, d_out, (size_t)N));
+  if (n_oob_out) TRY(d2h(c, n_oob_out, d_noob, (size_t)N));
+  return SBAG_OK;
+}
+
 int sbag_aggregate(sbag_ctx* c, const double* votes, int32_t L, int64_t N, int32_t agg, double* out) {
   if (!c || !votes || !out || L <= 0 || N < 0) return fail(SBAG_EINVAL, "bad arguments");
   if (agg != SBAG_AGG_MEAN && agg != SBAG_AGG_MODE) return fail(SBAG_EINVAL, "unknown aggregation");

@@ -315,6 +315,29 @@ size_t predict_tiled_lds(const PredictArgs& a);
 void launch_quantize(hipStream_t st, const double* X, int64_t n, int32_t F, const double* thr,
                      const int64_t* toff, uint16_t* codes, int32_t S);
 void launch_predict_tiled(hipStream_t st, const PredictArgs& a);
+// ---- out-of-bag prediction (sbag_oob.hip): the forest's aggregation restricted, row by
+// row, to the learners whose bag left the row out (counts == 0).  The learners go in
+// batches [t0, t1) in learner order; between batches a row's state lives in global memory:
+// out[row] the running sum (mean) or running mode, n_oob[row] the out-of-bag learners so
+// far, and for the mode gmax[row] the running maximum count and gcnt the class counters.
+struct OobArgs {
+  const uint8_t* counts;  // [t1 - t0][N] bag multiplicities of the batch's learners
+  int32_t t0, t1;         // the batch: trees [t0, t1) of the forest
+  int32_t first, last;    // first: the state starts at zero; last: out is finalized
+                          // (sum / n_oob or the mode, NaN where n_oob == 0)
+  int32_t* n_oob;         // [N]
+  int32_t* gmax;          // [N] (mode, several batches)
+  uint16_t* gcnt;         // u16 [nclasses][N] (mode, several batches)
+};
+// k_predict_oob: k_predict_tiled's geometry and LDS layout (predict_tiled_lds of `a` with
+// a.agg = kAggMean / kAggMode), a.out the running / final value
+void launch_predict_oob(hipStream_t st, const PredictArgs& a, const OobArgs& o);
+// k_aggregate_oob over a batch's per-tree predictions votes [K][N] (fp64) and bag counts
+// [K][N], rows in ranges of gcnt_rows for the mode (gcnt u16 [nclasses][gcnt_rows], zeroed
+// here when `first`; several batches: one range, gcnt_rows >= N)
+void launch_aggregate_oob(hipStream_t st, const double* votes, const uint8_t* counts, int K, int64_t N,
+                          int agg, int nclasses, double* out, int32_t* n_oob, int32_t* gmax,
+                          uint16_t* gcnt, int64_t gcnt_rows, bool first, bool last);
 // class-tile grouping of gini histogram entries (one workgroup per piece)
 // the grouping with known (segment, tile) sizes: cursors[q ntc + t] start at the tile's first
 // position and advance by atomics; pieces of tile_scatter_known_piece() entries

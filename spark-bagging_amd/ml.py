@@ -476,11 +476,55 @@ class _BaggingEstimator(_BaggingParams):
         model._copy_params_from(self)
         model.fit_timing = timings
         model.train_log = train_log
+        model.learner_range = (lb0, le0)  # the bags of a fit_range shard are those of its learners
         return model
 
 
 def _learner_shards(L, k):
     return [(i * L // k, (i + 1) * L // k) for i in range(k)]
+
+
+_OOB_METRICS = {False: ("rmse", "mse", "mae", "r2"), True: ("accuracy",)}
+
+
+def oob_metrics(pred, n_oob, y, classification, metricName=None):
+    """The out-of-bag score of `_BaggingModel.oobScore` from out-of-bag predictions (host
+    arrays, numpy only): {"metric", "value", "coverage", "numRows"}.  coverage is the
+    fraction of rows some learner left out (n_oob > 0); every metric is taken over those
+    rows only and is NaN when there are none.  Regression: rmse (default) =
+    sqrt(mean(e*e)), mse, mae, r2 = 1 - sum(e*e) / sum((y - mean(y))**2) with e = pred - y;
+    classification: accuracy = mean(pred == y)."""
+    classification = bool(classification)
+    metric = metricName or _OOB_METRICS[classification][0]
+    if metric not in _OOB_METRICS[classification]:
+        raise nat.IllegalArgumentException(
+            nat.SBAG_EINVAL, f"metricName given invalid value {metric} "
+                             f"(one of {', '.join(_OOB_METRICS[classification])})")
+    pred = np.asarray(pred, np.float64)
+    y = np.asarray(y, np.float64)
+    n_oob = np.asarray(n_oob)
+    if not (pred.shape == y.shape == n_oob.shape and pred.ndim == 1):
+        raise nat.IllegalArgumentException(nat.SBAG_EINVAL, "pred, n_oob and y differ in length")
+    covered = n_oob > 0
+    n = int(len(y))
+    res = {"metric": metric, "value": float("nan"),
+           "coverage": float(covered.sum()) / n if n else 0.0, "numRows": n}
+    if not covered.any():
+        return res
+    p, t = pred[covered], y[covered]
+    e = p - t
+    if metric == "accuracy":
+        v = np.mean(p == t)
+    elif metric == "rmse":
+        v = np.sqrt(np.mean(e * e))
+    elif metric == "mse":
+        v = np.mean(e * e)
+    elif metric == "mae":
+        v = np.mean(np.abs(e))
+    else:
+        v = 1 - np.sum(e * e) / np.sum((t - np.mean(t)) ** 2)
+    res["value"] = float(v)
+    return res
 
 
 class _BaggingModel(_BaggingParams):
@@ -493,6 +537,9 @@ class _BaggingModel(_BaggingParams):
         self._forest = None
         self.fit_timing = []
         self.train_log = None
+        # global learner indices of the models (learner i drew its bag with seed + i); None:
+        # (0, numBaseModels), a whole ensemble (a loaded model)
+        self.learner_range = None
 
     @property
     def numBaseModels(self):
@@ -543,6 +590,44 @@ class _BaggingModel(_BaggingParams):
         nat.predict_dataset_device(ds.ctx, forest, ds, nat.OUT_VOTES, 8, buf.data_ptr())
         torch.cuda.synchronize(dev)
         return pred, buf.cpu().numpy()
+
+    def oobPredictions(self, dataset, partition_offsets=None):
+        """Out-of-bag predictions on the training data: (pred, n_oob).  Row r is
+        aggregated over the learners whose bag (bfunctions.bag of the model's seed,
+        replacement and sampleRatio, regenerated on the device) did not draw it; n_oob[r]
+        counts them and pred[r] is NaN where there is none.  `dataset` is the Frame (its own
+        partition_offsets are used) or the DeviceDataset (with `partition_offsets`) the
+        model was fitted on."""
+        lb, le = self.learner_range or (0, self.numBaseModels)
+        if le - lb != self.numBaseModels:
+            raise nat.IllegalArgumentException(
+                nat.SBAG_EINVAL, f"learner range {(lb, le)} does not hold {self.numBaseModels} models")
+        if isinstance(dataset, nat.DeviceDataset):
+            ds, part, own = dataset, partition_offsets, False
+        else:
+            if not isinstance(dataset, Frame):
+                X, y = dataset
+                dataset = Frame(X, y, partition_offsets)
+            ds, part, own = dataset.device_dataset(nat.default_context(0)), dataset.partition_offsets, True
+        try:
+            return nat.predict_oob(ds.ctx, self.native_forest(), ds, replacement=self.get("replacement"),
+                                   sample_ratio=self.get("sampleRatio"), seed=self.get("seed"),
+                                   learner_begin=lb, learner_end=le, partition_offsets=part,
+                                   agg=self._agg)
+        finally:
+            if own:
+                ds.free()
+
+    def oobScore(self, dataset, metricName=None, partition_offsets=None):
+        """The out-of-bag estimate of the model's error on its training data (oob_metrics of
+        oobPredictions against the dataset's labels): {"metric", "value", "coverage",
+        "numRows"}."""
+        pred, n_oob = self.oobPredictions(dataset, partition_offsets)
+        if isinstance(dataset, nat.DeviceDataset):
+            y = dataset.labels()
+        else:
+            y = dataset.label if isinstance(dataset, Frame) else dataset[1]
+        return oob_metrics(pred, n_oob, y, self._agg == nat.AGG_MODE, metricName)
 
     def predict(self, features):
         """Single-vector predict (BaggingRegressor.scala:248-256 / BaggingClassifier.scala:248-257)."""
