@@ -225,6 +225,10 @@ typedef struct {
   double root_ms;          /* root histogram as an int8 MFMA contraction (k_hist_mfma);
                               0 when the root went through k_hist_rl (then in hist_ms)     */
   double root_mfma_ops;    /* its int8 operations (2 x 32^3 per MFMA)                      */
+  int64_t hist_midrun_flushes; /* flushes of a workgroup's LDS histogram in the middle of one
+                              node's run of pieces, caused by the packed word's entry limit
+                              alone (0 unless one workgroup holds more than flush_limit
+                              entries of a node; SBAG_HIST_FLUSH_LIMIT lowers the limit)    */
 } sbag_timing;
 int sbag_forest_timing(const sbag_forest* f, sbag_timing* out);
 

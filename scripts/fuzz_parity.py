@@ -5,7 +5,7 @@ fp64 labels for the fp64 engine, depth up to 14, several partitions), each fores
 against the CPU oracle node by node.  Runs until the time budget is spent; prints one line
 per case so a failure names its seed and replays with --start SEED --cases 1.
 
-usage: python3 scripts/fuzz_parity.py [--start S] [--minutes M] [--cases K]
+usage: python3 scripts/fuzz_parity.py [--start S] [--minutes M] [--cases K] [--labels]
 """
 import argparse
 import os
@@ -24,7 +24,8 @@ import sbag_loader  # noqa: E402
 sb = sbag_loader.load()
 nat = sb._native
 import oracle  # noqa: E402
-from parity_utils import assert_forest_equal, fuzz_case, fuzz_case_big, oracle_forest  # noqa: E402
+from parity_utils import (assert_forest_equal, fuzz_case, fuzz_case_big, fuzz_case_labels,  # noqa: E402
+                          oracle_forest)
 
 
 draw = fuzz_case  # tests/parity_utils.py
@@ -33,8 +34,11 @@ draw = fuzz_case  # tests/parity_utils.py
 draw_big = fuzz_case_big  # tests/parity_utils.py
 
 
-def run(ctx, seed, extra=False, big=False):
-    X, y, cls, f64, part, p, kind = (draw_big if big else draw)(seed)
+def run(ctx, seed, extra=False, big=False, labels=False):
+    case = fuzz_case_labels(seed) if labels else (draw_big if big else draw)(seed)
+    if case is None:
+        return True, f"seed {seed} (a classification draw: skipped)"
+    X, y, cls, f64, part, p, kind = case
     sd = oracle.DEFAULT_SEED_CLASSIFIER if cls else oracle.DEFAULT_SEED_REGRESSOR
     N, F = X.shape
     # --extra: a learner range that does not start at 0 and, half the time, a subspace
@@ -69,6 +73,14 @@ def run(ctx, seed, extra=False, big=False):
     subs = [oracle.subspace(sub_ratio, F, sd + i) for i in range(lb, lb + p["L"])]
     orf = oracle_forest(X, y, counts, subs, p["depth"], p["bins"], cls, p["min_inst"], p["min_gain"],
                         part=part)
+    if labels:  # which engine took it, and the label image the packed word has to hold
+        t = forest.timing()
+        sh = 0  # the smallest shift at which every label is an integer
+        while sh < 60 and (np.ldexp(y, sh) != np.rint(np.ldexp(y, sh))).any():
+            sh += 1
+        k = np.rint(np.ldexp(y, sh)).astype(np.int64)
+        desc += (f" | engine {'fp64' if t['chain_ms'] > 0 else 'int'} shift {sh} k [{k.min()}, {k.max()}] "
+                 f"cmax {int(counts.max())} midrun {t['hist_midrun_flushes']}")
     try:
         assert_forest_equal(forest, orf)
         agg = nat.AGG_MODE if cls else nat.AGG_MEAN
@@ -125,6 +137,8 @@ def main():
                     help="learner offsets, subspace ratios of their own, device transform")
     ap.add_argument("--big", action="store_true", help="1-3M rows, 16-32 learners (draw_big)")
     ap.add_argument("--booster", action="store_true", help="GBM base learners (run_booster)")
+    ap.add_argument("--labels", action="store_true",
+                    help="regression draws with the label magnitude fuzzed (fuzz_case_labels)")
     a = ap.parse_args()
     ctx = sb.default_context(0)
     t0 = time.time()
@@ -132,7 +146,7 @@ def main():
     seed = a.start
     while n < a.cases and time.time() - t0 < 60 * a.minutes:
         t1 = time.time()
-        ok, desc = run_booster(ctx, seed) if a.booster else run(ctx, seed, a.extra, a.big)
+        ok, desc = run_booster(ctx, seed) if a.booster else run(ctx, seed, a.extra, a.big, a.labels)
         n += 1
         fails += 0 if ok else 1
         print(("ok   " if ok else "FAIL ") + f"{time.time() - t1:6.1f}s " + desc, flush=True)

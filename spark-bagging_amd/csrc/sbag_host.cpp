@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "sbag.h"
+#include "sbag_budget.h"
 #include "sbag_fastmath.h"
 #include "sbag_internal.h"
 
@@ -1506,6 +1507,43 @@ static void build_work(const std::vector<std::pair<int64_t, int64_t>>& segs, int
   w.entries = (double)tot;
 }
 
+// Flushes of one histogram launch that flush_limit alone causes (sbag_timing.
+// hist_midrun_flushes): each workgroup's piece range walked with the kernels' own rule --
+// k_hist and k_hist_rl flush before a piece when `slot != cur_slot || tile != cur_tile ||
+// acc + (b - a) > A.flush_limit` (sbag_kernels.hip:1358 in k_hist's piece loop and :1632 in
+// k_hist_rl's; a change to either rule belongs here too) -- and only the flushes of the last
+// clause counted.  Pieces must carry their parents' slot and
+// tile (upload_work); `grouped` as HistArgs.grouped (else every tile is 0).  Counted once per
+// workgroup column: the grid's feature and class tiles (blockIdx.y) repeat the same walk.
+// *stored: those of them in a run whose first flush stores (the piece's `excl`: cur_store),
+// so that the later ones add to what the workgroup itself wrote (SBAG_LEVEL_TRACE prints it).
+static int64_t count_midrun_flushes(const HistWork& w, int64_t flush_limit, bool grouped,
+                                    int64_t* stored = nullptr) {
+  int64_t n = 0, ns = 0;
+  for (int g = 0; g < w.nwg; g++) {
+    int cur_slot = -1, cur_tile = -1;
+    int64_t acc = 0;
+    for (int p = w.wg[g]; p < w.wg[g + 1]; p++) {
+      const HistChunk& pc = w.pieces[p];
+      if (pc.fr <= 0 || pc.slot < 0) continue;
+      const int tile = grouped ? pc.tile : 0;
+      const int64_t len = pc.b - pc.a;
+      if (pc.slot != cur_slot || tile != cur_tile || acc + len > flush_limit) {
+        if (pc.slot == cur_slot && tile == cur_tile) {
+          n++;
+          ns += pc.excl ? 1 : 0;
+        }
+        cur_slot = pc.slot;
+        cur_tile = tile;
+        acc = 0;
+      }
+      acc += len;
+    }
+  }
+  if (stored) *stored = ns;
+  return n;
+}
+
 // fit_range's request to be called again on halves of its learner range: per-replica bins
 // (thresholds that differ across replicas) of all its replicas exceed the device budget
 static constexpr int kSplitRange = -1000;
@@ -1580,6 +1618,7 @@ static void merge_forests(sbag_forest* fa, sbag_forest* fb) {
   T.exact_fallbacks += U.exact_fallbacks;
   T.hist_lds_atomics += U.hist_lds_atomics;
   T.group_ms += U.group_ms;
+  T.hist_midrun_flushes += U.hist_midrun_flushes;
 }
 
 // Two learner parts run side by side only when both workspaces fit the device next to what
@@ -2895,39 +2934,26 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
       return fail(SBAG_EUNSUPPORTED, "class counts exceed 32 bits");
   }
   // ---- LDS packing: count field at bit cshift, flush_limit entries between flushes
+  // (hist_word_budget, sbag_budget.h: the search for flush_limit, the raise to cshift = 32 and
+  // the 2^53 bound.  SBAG_HIST_FLUSH_LIMIT=n starts the search at n rounded down to a power of
+  // two in [256, 2^22], so it only ever lowers the limit: tests reach the flushes the limit
+  // alone causes at small shapes with it.  Read per fit.)
   const int64_t K0 = -lkmin;
-  const double kspan = (double)(lkmax - lkmin + 1);
-  const double kabs = (double)std::max(std::llabs(lkmin), std::llabs(lkmax));
-  int64_t flush_limit = (int64_t)1 << 22;
-  int cshift = 40;
-  for (;; flush_limit /= 2) {
-    if (flush_limit < 256) {
-      if (!gini && !f64) {
-        (void)hipEventDestroy(ev_start);
-        (void)hipEventDestroy(ev_stop);
-        return kIntRange;
-      }
-      return fail(SBAG_EUNSUPPORTED, "label range too wide for the packed LDS histogram");
-    }
-    const double wmax = (double)flush_limit * cmax;
-    if (gini) {
-      if (wmax < 4294967295.0) break;
-      continue;
-    }
-    cshift = (int)std::ceil(std::log2(wmax * kspan + 1.0));
-    const int cbits = 64 - cshift;
-    // (the sum-of-squares plane of the exact fallback needs wmax k^2 in 64 bits; the fp64
-    // path never builds it)
-    if (cbits >= 1 && std::ldexp(1.0, cbits) > wmax && (f64 || wmax * kabs * kabs < 1.8e19)) break;
+  int64_t flush_start = (int64_t)1 << 22;
+  if (const char* fl_env = getenv("SBAG_HIST_FLUSH_LIMIT")) {
+    const long long want = std::max(256LL, std::min((long long)flush_start, atoll(fl_env)));
+    while (flush_start > want) flush_start /= 2;
   }
-  // the row-lane histogram builds the word as (c << cshift) + c*(k + K0) with a 32-bit
-  // low half: raise cshift to 32 when the count field keeps room for flush_limit * cmax
-  if (!gini && cshift < 32 && (double)flush_limit * cmax < 4294967296.0) cshift = 32;
-  if (!gini && !f64 && (double)N * cmax * kabs * kabs >= std::ldexp(1.0, 53)) {
+  const HistWordBudget budget = hist_word_budget(lkmin, lkmax, cmax, N, gini, f64, flush_start);
+  if (budget.int_range) {
     (void)hipEventDestroy(ev_start);
     (void)hipEventDestroy(ev_stop);
     return kIntRange;
   }
+  if (budget.flush_limit == 0)
+    return fail(SBAG_EUNSUPPORTED, "label range too wide for the packed LDS histogram");
+  const int64_t flush_limit = budget.flush_limit;
+  const int cshift = budget.cshift;
 
   // ---- per-replica tables
   std::vector<int32_t> h_sub((size_t)R * Fmax, 0), h_Fr(R);
@@ -2992,6 +3018,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
   ha.cshift = cshift;
   ha.flush_limit = flush_limit;
   double hist_entries = 0, hist_alg_bytes = 0, hist_upper = 0, hist_work = 0, hist_lds = 0;
+  int64_t hist_midrun = 0;  // flushes flush_limit alone caused (count_midrun_flushes)
   const int s_y = gini ? 1 : 4;  // label bytes per row in SURVEY 8d (u8 class / fp32 label)
   // SURVEY §8d work bytes of the histograms of a set of node segments
   auto add_work = [&](const std::vector<std::pair<int64_t, int64_t>>& segs,
@@ -3264,9 +3291,12 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
       (void)hipEventElapsedTime(&ms, tm.ev[h].second.first, tm.ev[h].second.second);
       int64_t ne = 0;
       for (auto& sg : segs) ne += sg.second - sg.first;
-      fprintf(stderr, "[sbag] level %d cat %d mode %d grouped %d segs %zu entries %lld pieces %zu nwg %d ms %.3f\n",
+      int64_t mid_stored = 0;
+      const int64_t mid = count_midrun_flushes(work, flush_limit, grouped, &mid_stored);
+      fprintf(stderr, "[sbag] level %d cat %d mode %d grouped %d segs %zu entries %lld pieces %zu nwg %d ms %.3f "
+                      "limit flushes %lld (%lld after a store) zero plan %d\n",
               trace_level, cat, mode, grouped ? 1 : 0, segs.size(), (long long)ne, work.pieces.size(),
-              work.nwg, ms);
+              work.nwg, ms, (long long)mid, (long long)mid_stored, zplan ? 1 : 0);
     }
     if (trace && getenv("SBAG_HIST_ABLATE")) {
       // diagnostics: relaunch the same histogram with phases skipped (flushes always
@@ -3292,6 +3322,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
     ha.grouped = 0;
     if (cat == T_HIST) {
       hist_launches++;
+      hist_midrun += count_midrun_flushes(work, flush_limit, grouped);
       // LDS atomic wave-instructions per entry: per feature tile, k_hist one per 64-lane
       // group, k_hist_rl K/4 (16 lanes of K features per entry, 4 entries per instruction)
       const double per_entry =
@@ -4119,6 +4150,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
     T.fix_ms = cats[T_FIX];
     T.exact_fallbacks = G.fallbacks;
     T.hist_launches = hist_launches;
+    T.hist_midrun_flushes = hist_midrun;
     T.hist_alg_bytes = hist_alg_bytes;
     T.hist_entries = hist_entries;
     T.hist_lds_atomics = hist_lds;
@@ -4810,6 +4842,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
   T.root_mfma_ops = root_mfma_ops;
   T.exact_fallbacks = fallbacks;
   T.hist_launches = hist_launches;
+  T.hist_midrun_flushes = hist_midrun;
   T.hist_alg_bytes = hist_alg_bytes;
   T.hist_entries = hist_entries;
   T.hist_lds_atomics = hist_lds;

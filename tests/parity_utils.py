@@ -87,6 +87,32 @@ def fuzz_case(seed):
     return X, y, cls, f64, part, p, kind
 
 
+def fuzz_case_labels(seed):
+    """--labels: fuzz_case(seed)'s regression draws with the label magnitude fuzzed too
+    (fuzz_case keeps |k| near 2^11): the labels' integer grid image k0 (units of 1/32) is
+    moved by an offset of up to 2^22 grid units and scaled by 2^e, e in [-30, 12], so the
+    labels stay dyadic with |k| < 2^23 at every shift the engine accepts (<= 35 here).
+    Small offsets stay on the integer engine, large ones pass N cmax kabs^2 = 2^53 and go
+    to the fp64 engine; kspan stays fuzz_case's, so K0 moves far from zero.  The rescaling
+    draws from a stream of its own, so every seed's other draws stay put.  None for a
+    classification draw."""
+    X, y, cls, f64, part, p, kind = fuzz_case(seed)
+    if cls:
+        return None
+    rng = np.random.default_rng(seed + 3 * 10**7)
+    # the labels' grid: fuzz_case's dyadic labels are multiples of 1/32 (its fp64 draws are
+    # those times 1.1 plus 0.3: taken back to the grid)
+    k0 = np.rint(((y - 0.3) / 1.1 if f64 else y) * 32.0).astype(np.int64)
+    e = int(rng.integers(-30, 13))
+    up = max(0, e - 5)  # integer labels: the image is (k0 + off) 2^up
+    off_max = min(2**22, 2 ** (23 - up) - int(np.abs(k0).max()) - 1)
+    off = int(rng.choice([-1, 1])) * int(2.0 ** rng.uniform(0.0, np.log2(off_max)))
+    k = k0 + off
+    assert int(np.abs(k).max()) * 2**up < 2**23
+    y2 = np.ldexp(k.astype(np.float64), e - 5)
+    return X, y2, False, False, part, p, kind
+
+
 def fuzz_case_big(seed):
     """--big: 1-3M rows and 16-32 learners, so the fit splits its learner range into two
     halves on two streams and the histograms run at shard-like sizes."""
