@@ -258,6 +258,40 @@ int sbag_predict_oob(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* ds
                      const sbag_sampler_params* sampler, const int64_t* partition_offsets,
                      int32_t num_partitions, int32_t agg, double* out /* host [num_rows] */,
                      int32_t* n_oob_out /* host [num_rows] or NULL */);
+/* Out-of-bag predictions under permuted features: the device side of Breiman's permutation
+   importance.  `ds`, `sampler`, `partition_offsets` and `agg` are sbag_predict_oob's (same
+   validation, same error codes); base_out and n_oob_out are its out and n_oob_out, byte
+   for byte.  out[k][r] is the same out-of-bag aggregation of row r (the learners with
+   counts[i][r] == 0, in learner order, MEAN / MODE as above, NaN where n_oob[r] == 0) with
+   one change: every tree reads feature features[k] of row r from row src_rows[k][r]; all
+   other features are row r's own.  The substitution is made in the dataset's code space
+   (both rows share the feature's dictionary, so it is exact); a tree whose subspace lacks
+   the feature is unaffected.  src_rows[k] may be any map into [0, num_rows): a permutation,
+   a shuffle within partitions or strata, a constant; the identity reproduces base_out's
+   bytes.  A feature may appear in several slots, each with its own src_rows row.
+   num_perm == 0 writes base_out / n_oob_out only.  SBAG_EINVAL: a feature outside
+   [0, num_features), a source row outside [0, num_rows) (checked before any result is
+   written; the context stays usable), num_perm < 0, or a null features / src_rows / out
+   with num_perm > 0.  SBAG_EUNSUPPORTED: num_rows > INT32_MAX.
+   u8 / u16 datasets whose trees fit the LDS go through one fused pass per feature batch
+   (up to 64 slots, as many as the LDS holds; SBAG_OOBP_BATCH_FEATURES lowers it): a row's
+   walk through a tree notes which of the batch's features it tested and walks again only
+   for those, every other slot taking the baseline vote (the same bits).  Everything else
+   (u32 codes, trees past the LDS chunk, more classes than the LDS counts), and every call
+   under SBAG_OOBP_FORCE_FALLBACK=1, substitutes the column in a copy of the dataset's codes
+   and runs a plain out-of-bag pass per slot: the same bytes, slower.  Learner batches as
+   in sbag_predict_oob; SBAG_AGG_MODE over several batches carries 2 x classes x num_rows x
+   (slots + 1) bytes of counters, the slots lowered to fit 256 MB and SBAG_EUNSUPPORTED when
+   one slot does not. */
+int sbag_predict_oob_permuted(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* ds,
+                              const sbag_sampler_params* sampler, const int64_t* partition_offsets,
+                              int32_t num_partitions, int32_t agg,
+                              const int32_t* features /* host [num_perm] global feature indices */,
+                              int32_t num_perm,
+                              const int32_t* src_rows /* host [num_perm x num_rows] */,
+                              double* out /* host [num_perm x num_rows] */,
+                              double* base_out /* host [num_rows] or NULL */,
+                              int32_t* n_oob_out /* host [num_rows] or NULL */);
 /* ordered aggregation of per-learner predictions on the host:
    votes [num_learners x num_rows] fp64, learner order */
 int sbag_aggregate(sbag_ctx* ctx, const double* votes, int32_t num_learners, int64_t num_rows,

@@ -11,6 +11,7 @@ from ._native import (Context, DeviceDataset, NativeForest, IllegalArgumentExcep
 from .libsvm import SparseRows, load_libsvm  # noqa: F401
 from .ml import (BaggingClassificationModel, BaggingClassifier, BaggingRegressionModel,  # noqa: F401
                  BaggingRegressor, DecisionTreeClassifier, DecisionTreeModel,
-                 DecisionTreeRegressor, Frame, even_partitions, java_string_hash, oob_metrics)
+                 DecisionTreeRegressor, Frame, even_partitions, java_string_hash, oob_metrics,
+                 oob_permutation_importance, permutation_source_rows)
 from .gbm import (GBMClassificationModel, GBMClassifier, GBMRegressionModel,  # noqa: F401
                   GBMRegressor)

@@ -29,7 +29,7 @@ EXPORTED = [
     "sbag_fit", "sbag_fit_booster", "sbag_forest_num_trees", "sbag_forest_tree_info", "sbag_forest_subspace",
     "sbag_forest_nodes", "sbag_forest_create", "sbag_forest_free", "sbag_forest_timing",
     "sbag_predict", "sbag_predict_dataset", "sbag_aggregate", "sbag_predict_dataset_device",
-    "sbag_aggregate_device", "sbag_predict_oob",
+    "sbag_aggregate_device", "sbag_predict_oob", "sbag_predict_oob_permuted",
 ]
 
 
@@ -151,6 +151,8 @@ def lib():
             "sbag_predict_dataset_device": [P, P, P, i32, i32, P],
             "sbag_aggregate_device": [P, P, i32, i32, i64, i32, i32, i32, P],
             "sbag_predict_oob": [P, P, P, ctypes.POINTER(SamplerParams), P, i32, i32, P, P],
+            "sbag_predict_oob_permuted": [P, P, P, ctypes.POINTER(SamplerParams), P, i32, i32, P, i32, P, P,
+                                          P, P],
         }
         for name, args in sig.items():
             fn = getattr(L, name)
@@ -528,6 +530,30 @@ def predict_oob(ctx, forest, dataset, *, replacement, sample_ratio, seed, learne
     check(lib().sbag_predict_oob(ctx.handle, forest.handle, dataset.handle, ctypes.byref(p), ptr(off),
                                  P, agg, ptr(out), ptr(n_oob)))
     return out, n_oob
+
+
+def predict_oob_permuted(ctx, forest, dataset, *, replacement, sample_ratio, seed, learner_begin, learner_end,
+                         partition_offsets=None, agg, features, src_rows):
+    """Out-of-bag predictions under permuted features (sbag_predict_oob_permuted): slot k is
+    predict_oob with feature features[k] of row r read from row src_rows[k][r] (int32
+    [K, N], any map into [0, N)).  Returns (perm_pred fp64 [K, N], base_pred fp64 [N],
+    n_oob int32 [N]); base_pred and n_oob are predict_oob's."""
+    p = SamplerParams(int(replacement), 0, float(sample_ratio), int(seed), learner_begin, learner_end)
+    off = None
+    P = 1
+    if partition_offsets is not None:
+        off = np.ascontiguousarray(partition_offsets, np.int64)
+        P = len(off) - 1
+    n = dataset.shape[0]
+    feats = np.ascontiguousarray(features, np.int32).reshape(-1)
+    K = len(feats)
+    src = np.ascontiguousarray(src_rows, np.int32).reshape(K, n)
+    out = np.zeros((K, n), np.float64)
+    base = np.zeros(n, np.float64)
+    n_oob = np.zeros(n, np.int32)
+    check(lib().sbag_predict_oob_permuted(ctx.handle, forest.handle, dataset.handle, ctypes.byref(p), ptr(off),
+                                          P, agg, ptr(feats), K, ptr(src), ptr(out), ptr(base), ptr(n_oob)))
+    return out, base, n_oob
 
 
 def aggregate(ctx, votes, agg):

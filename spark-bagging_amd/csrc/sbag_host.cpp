@@ -5030,12 +5030,13 @@ struct TiledPlan {
 };
 
 template <typename TC>
-static bool plan_tiled(const sbag_forest* f, PredictArgs& pa, int F, TC tc_of, TiledPlan& P) {
+static bool plan_tiled(const sbag_forest* f, PredictArgs& pa, int F, TC tc_of, TiledPlan& P,
+                       size_t extra_fixed = 0 /* LDS the kernel holds besides predict_tiled_lds */) {
   const int L = (int)f->trees.size();
   pa.L = L;
   pa.nclasses = std::max(f->nclasses, 1);
   pa.chunk_bytes = 0;
-  const size_t fixed = predict_tiled_lds(pa);
+  const size_t fixed = predict_tiled_lds(pa) + extra_fixed;
   const size_t lds_cap = 160 * 1024 - 512;
   if (F >= 32768 || fixed + 4096 > lds_cap) return false;
   const int budget = (int)std::min<size_t>(64 * 1024, lds_cap - fixed) & ~15;
@@ -5391,6 +5392,233 @@ int sbag_predict_oob(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds,
   }
   TRY(d2h(c, out, d_out, (size_t)N));
   if (n_oob_out) TRY(d2h(c, n_oob_out, d_noob, (size_t)N));
+  return SBAG_OK;
+}
+
+// Out-of-bag predictions under permuted features (permutation importances): slot k is
+// sbag_predict_oob with feature features[k] of row r read from row src_rows[k][r].  The
+// slots go through k_predict_oob_perm in feature batches of KB <= 64, KB being what the LDS
+// holds beside the row tile, the slot tables and a useful forest chunk (the largest tree, at
+// least 16 KB); SBAG_OOBP_BATCH_FEATURES lowers it (read on every call).  Where plan_tiled
+// refuses, or with SBAG_OOBP_FORCE_FALLBACK=1, every slot is a plain out-of-bag pass of the
+// global-memory walk over a copy of the code matrix with that one column substituted.  The
+// sampler runs again per (feature batch, learner batch).
+int sbag_predict_oob_permuted(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds,
+                              const sbag_sampler_params* sp, const int64_t* partition_offsets, int32_t P,
+                              int32_t agg, const int32_t* features, int32_t num_perm,
+                              const int32_t* src_rows, double* out, double* base_out, int32_t* n_oob_out) {
+  if (!c || !f || !ds || !sp) return fail(SBAG_EINVAL, "bad arguments");
+  if (num_perm < 0 || (num_perm > 0 && (!features || !src_rows || !out)))
+    return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(check_sampler(sp));
+  TRY(check_agg(f, agg));
+  const int L = (int)f->trees.size();
+  if (sp->learner_end - sp->learner_begin != L)
+    return fail(SBAG_EINVAL, "the sampler's learner range holds " +
+                                 std::to_string(sp->learner_end - sp->learner_begin) +
+                                 " learners, the forest " + std::to_string(L) + " trees");
+  const int64_t N = ds->N;
+  if (partition_offsets && P >= 1 && partition_offsets[P] != N)
+    return fail(SBAG_EINVAL, "partition_offsets must end at the dataset's row count");
+  std::vector<int64_t> poff;
+  TRY(check_partitions(P, partition_offsets, N, poff));
+  for (const HTree& t : f->trees)
+    for (int32_t g : t.sub)
+      if (g >= ds->F) return fail(SBAG_EINVAL, "dataset has fewer features than the model");
+  if (ds->ctx->device != c->device)
+    return fail(SBAG_EINVAL, "dataset lives on device " + std::to_string(ds->ctx->device) +
+                                 ", the context on device " + std::to_string(c->device));
+  if (N > (int64_t)INT32_MAX)
+    return fail(SBAG_EUNSUPPORTED, "permuted out-of-bag predictions index source rows by int32: " +
+                                       std::to_string(N) + " rows");
+  for (int k = 0; k < num_perm; k++)
+    if (features[k] < 0 || features[k] >= ds->F)
+      return fail(SBAG_EINVAL, "features[" + std::to_string(k) + "] = " + std::to_string(features[k]) +
+                                   " is outside the dataset's " + std::to_string(ds->F) + " features");
+  // every source row is checked before any kernel gathers through it
+  for (int k = 0; k < num_perm; k++) {
+    const int32_t* s = src_rows + (int64_t)k * N;
+    uint32_t bad = 0;
+    for (int64_t r = 0; r < N; r++) bad |= (uint32_t)((uint32_t)s[r] >= (uint32_t)N);
+    if (bad)
+      return fail(SBAG_EINVAL, "src_rows[" + std::to_string(k) + "] holds a row outside [0, " +
+                                   std::to_string(N) + ")");
+  }
+  if (N == 0) return SBAG_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const int ncls = std::max(f->nclasses, 1);
+  const bool mode_agg = agg == SBAG_AGG_MODE;
+  PredictArgs pa{};
+  pa.code_bytes = ds->code_bytes;
+  pa.S = ds->S;
+  pa.N = N;
+  pa.agg = agg;
+  pa.nclasses = ncls;
+  TiledPlan Pl;
+  bool tiled = false;
+  int KB = 0;
+  const char* ffb = getenv("SBAG_OOBP_FORCE_FALLBACK");
+  if (!(ffb && atoi(ffb) != 0) && ds->code_bytes != 4) {
+    size_t max_tree = 0;
+    for (const HTree& t : f->trees) {
+      size_t leaves = 0;
+      for (const sbag_node& n : t.nodes) leaves += n.left < 0;
+      max_tree = std::max(max_tree, (t.nodes.size() + leaves) * 8);
+    }
+    const size_t lds_cap = 160 * 1024 - 512;
+    const size_t base = predict_tiled_lds(pa) + oobperm_lds_fixed(ds->F);
+    const size_t slot = oobperm_lds_slot(ds->code_bytes, agg, ncls);
+    const size_t useful = std::min<size_t>(64 * 1024, std::max<size_t>(max_tree, 16 * 1024));
+    int64_t fit = 0;  // slots beside a useful chunk, else beside the largest tree
+    if (base + useful + slot <= lds_cap) fit = (int64_t)((lds_cap - base - useful) / slot);
+    else if (base + std::max<size_t>(max_tree, 4096) + slot <= lds_cap)
+      fit = (int64_t)((lds_cap - base - std::max<size_t>(max_tree, 4096)) / slot);
+    if (num_perm == 0 || fit >= 1) {
+      KB = (int)std::min<int64_t>({fit, (int64_t)kOobPermSlots, (int64_t)num_perm});
+      if (const char* e = getenv("SBAG_OOBP_BATCH_FEATURES")) KB = std::max(std::min(KB, 1), std::min(KB, atoi(e)));
+      if (KB > 0) KB = (num_perm + (num_perm + KB - 1) / KB - 1) / ((num_perm + KB - 1) / KB);  // even batches
+      tiled = plan_tiled(f, pa, ds->F, [&](int g, double thr) {
+        const std::vector<double>& d = ds->dict[g];
+        return (int64_t)(std::upper_bound(d.begin(), d.end(), thr) - d.begin()) - 1;
+      }, Pl, oobperm_lds_fixed(ds->F) + (size_t)KB * slot);
+    }
+  }
+  // learner batches as sbag_predict_oob's
+  const double per = (double)N * (tiled ? 1.0 : 9.0);
+  int batch = (int)std::max(1.0, std::min((double)L, std::floor(bins_budget(c) / per)));
+  if (const char* e = getenv("SBAG_OOB_BATCH_LEARNERS")) batch = std::max(1, std::min(L, atoi(e)));
+  const bool several = batch < L;
+  const int64_t cap_rows = std::max<int64_t>(256, ((int64_t)256 << 20) / (2 * ncls));
+  int64_t gcnt_rows = 0;
+  if (mode_agg && (several || !tiled)) {
+    if (several && N > cap_rows)
+      return fail(SBAG_EUNSUPPORTED,
+                  "out-of-bag mode over several learner batches needs " +
+                      std::to_string((int64_t)2 * ncls * N) + " bytes of carried class counters (limit 256 MB)");
+    gcnt_rows = std::min(N, cap_rows);
+  }
+  // (fused, several batches: the baseline's and the slots' counters share the 256 MB)
+  if (tiled && mode_agg && several)
+    while (KB > 1 && (int64_t)(KB + 1) * N > cap_rows) KB--;
+  if (tiled && mode_agg && several && num_perm > 0 && (int64_t)(KB + 1) * N > cap_rows)
+    return fail(SBAG_EUNSUPPORTED,
+                "permuted out-of-bag mode over several learner batches needs " +
+                    std::to_string((int64_t)4 * ncls * N) +
+                    " bytes of carried class counters for one feature (limit 256 MB)");
+  double* d_out;
+  int32_t *d_noob, *d_gmax = nullptr;
+  uint16_t* d_gcnt = nullptr;
+  uint8_t* d_counts;
+  TRY(ws_typed(c, "pout", (size_t)N, &d_out));
+  TRY(ws_typed(c, "oob_n", (size_t)N, &d_noob));
+  if (mode_agg) TRY(ws_typed(c, "oob_max", (size_t)N, &d_gmax));
+  if (gcnt_rows) TRY(ws_typed(c, "mode_cnt", (size_t)ncls * gcnt_rows, &d_gcnt));
+  TRY(ws_typed(c, "counts", (size_t)batch * N, &d_counts));
+  int32_t* d_src;
+  if (tiled) {
+    TRY(upload_plan(c, Pl, pa));
+    pa.codes = ds->d_codes;
+    pa.out = d_out;
+    const size_t kb1 = (size_t)std::max(KB, 1);
+    int32_t *d_feat, *d_pmax = nullptr;
+    double* d_pout;
+    uint16_t* d_pcnt = nullptr;
+    TRY(ws_typed(c, "oobp_src", kb1 * N, &d_src));
+    TRY(ws_typed(c, "oobp_feat", (size_t)kOobPermSlots, &d_feat));
+    TRY(ws_typed(c, "oobp_out", kb1 * N, &d_pout));
+    if (mode_agg && several) {
+      TRY(ws_typed(c, "oobp_max", kb1 * N, &d_pmax));
+      TRY(ws_typed(c, "oobp_cnt", kb1 * ncls * N, &d_pcnt));
+    }
+    int k0 = 0;
+    do {  // feature batches (one pass of the baseline alone when num_perm == 0)
+      const int kb = std::min(KB, num_perm - k0);
+      if (kb > 0) {
+        TRY(h2d(c, d_feat, features + k0, (size_t)kb));
+        TRY(h2d(c, d_src, src_rows + (int64_t)k0 * N, (size_t)kb * N));
+      }
+      for (int b0 = 0; b0 < L; b0 += batch) {
+        const int b1 = std::min(L, b0 + batch);
+        sbag_sampler_params sb = *sp;
+        sb.learner_begin = sp->learner_begin + b0;
+        sb.learner_end = sp->learner_begin + b1;
+        TRY(run_sampler(c, &sb, poff, N, d_counts, false));
+        OobArgs oa{};
+        oa.counts = d_counts;
+        oa.t0 = b0;
+        oa.t1 = b1;
+        oa.first = b0 == 0;
+        oa.last = b1 == L;
+        oa.n_oob = d_noob;
+        oa.gmax = d_gmax;
+        oa.gcnt = d_gcnt;
+        OobPermArgs qa{};
+        qa.src = d_src;
+        qa.feat = d_feat;
+        qa.kb = kb;
+        qa.F = ds->F;
+        qa.pout = d_pout;
+        qa.pmax = d_pmax;
+        qa.pcnt = d_pcnt;
+        launch_predict_oob_perm(c->stream, pa, oa, qa);
+        HIP_TRY(hipGetLastError());
+        if (sp->replacement) TRY(sampler_overflow(c));
+      }
+      if (kb > 0) TRY(d2h(c, out + (int64_t)k0 * N, d_pout, (size_t)kb * N));
+      if (k0 == 0) {
+        if (base_out) TRY(d2h(c, base_out, d_out, (size_t)N));
+        if (n_oob_out) TRY(d2h(c, n_oob_out, d_noob, (size_t)N));
+      }
+      k0 += kb;
+    } while (k0 < num_perm);
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SBAG_OK;
+  }
+  // fallback: plain out-of-bag passes of the global-memory walk, the slot's column
+  // substituted in a copy of the code matrix and restored afterwards
+  const DevNode* f_nodes = nullptr;
+  const int64_t* f_off = nullptr;
+  double* d_votes;
+  TRY(upload_forest(c, f, &f_nodes, &f_off));
+  TRY(ws_typed(c, "oob_votes", (size_t)batch * N, &d_votes));
+  auto oob_pass = [&](const void* codes) -> int {
+    for (int b0 = 0; b0 < L; b0 += batch) {
+      const int b1 = std::min(L, b0 + batch);
+      sbag_sampler_params sb = *sp;
+      sb.learner_begin = sp->learner_begin + b0;
+      sb.learner_end = sp->learner_begin + b1;
+      TRY(run_sampler(c, &sb, poff, N, d_counts, false));
+      launch_predict(c->stream, nullptr, codes, ds->code_bytes, ds->d_dict, ds->d_dict_off, N, ds->F, ds->S,
+                     f_nodes, f_off + b0, b1 - b0, kAggVotes, ncls, nullptr, nullptr, d_votes, 8, nullptr, 0);
+      HIP_TRY(hipGetLastError());
+      launch_aggregate_oob(c->stream, d_votes, d_counts, b1 - b0, N, agg, ncls, d_out, d_noob, d_gmax, d_gcnt,
+                           gcnt_rows, b0 == 0, b1 == L);
+      HIP_TRY(hipGetLastError());
+      if (sp->replacement) TRY(sampler_overflow(c));
+    }
+    return SBAG_OK;
+  };
+  TRY(oob_pass(ds->d_codes));
+  if (base_out) TRY(d2h(c, base_out, d_out, (size_t)N));
+  if (n_oob_out) TRY(d2h(c, n_oob_out, d_noob, (size_t)N));
+  if (num_perm > 0) {
+    void* d_copy;
+    const size_t code_bytes_all = (size_t)N * ds->S * ds->code_bytes;
+    TRY(ws_get(c, "oobp_codes", code_bytes_all, &d_copy));
+    TRY(ws_typed(c, "oobp_src", (size_t)N, &d_src));
+    HIP_TRY(hipMemcpyAsync(d_copy, ds->d_codes, code_bytes_all, hipMemcpyDeviceToDevice, c->stream));
+    for (int k = 0; k < num_perm; k++) {
+      TRY(h2d(c, d_src, src_rows + (int64_t)k * N, (size_t)N));
+      launch_permute_column(c->stream, d_copy, ds->d_codes, ds->code_bytes, N, ds->S, features[k], d_src);
+      HIP_TRY(hipGetLastError());
+      TRY(oob_pass(d_copy));
+      launch_permute_column(c->stream, d_copy, ds->d_codes, ds->code_bytes, N, ds->S, features[k], nullptr);
+      HIP_TRY(hipGetLastError());
+      TRY(d2h(c, out + (int64_t)k * N, d_out, (size_t)N));
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(c->stream));
   return SBAG_OK;
 }
 

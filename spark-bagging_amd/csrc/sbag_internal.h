@@ -338,6 +338,31 @@ void launch_predict_oob(hipStream_t st, const PredictArgs& a, const OobArgs& o);
 void launch_aggregate_oob(hipStream_t st, const double* votes, const uint8_t* counts, int K, int64_t N,
                           int agg, int nclasses, double* out, int32_t* n_oob, int32_t* gmax,
                           uint16_t* gcnt, int64_t gcnt_rows, bool first, bool last);
+// ---- out-of-bag predictions under permuted features (sbag_oobperm.hip): slot k of a
+// feature batch is sbag_predict_oob with feature feat[k] of row r taken from row src[k][r].
+// Between learner batches a slot's state lives in global memory as the baseline's does:
+// pout[k][row] the running sum / running mode, pmax[k][row] the running maximum count and
+// pcnt[k] the class counters; n_oob is the baseline's (OobArgs), shared by all slots.
+constexpr int kOobPermSlots = 64;  // slots of one launch (a u64 slot set per feature)
+struct OobPermArgs {
+  const int32_t* src;   // [kb][N] source rows, each in [0, N)
+  const int32_t* feat;  // [kb] global feature of each slot, each in [0, F)
+  int32_t kb, F;
+  double* pout;         // [kb][N] running / final value of each slot
+  int32_t* pmax;        // [kb][N] (mode, several batches)
+  uint16_t* pcnt;       // u16 [kb][nclasses][N] (mode, several batches)
+};
+// LDS of k_predict_oob_perm past predict_tiled_lds: the feature -> slot-set table and the
+// slots' features, and per slot the permuted codes of the tile and its accumulators
+size_t oobperm_lds_fixed(int F);
+size_t oobperm_lds_slot(int code_bytes, int agg, int nclasses);
+// k_predict_oob_perm: k_predict_oob (same `a` and `o`: a.out / o.n_oob are the unpermuted
+// baseline) plus q.kb <= kOobPermSlots slots
+void launch_predict_oob_perm(hipStream_t st, const PredictArgs& a, const OobArgs& o, const OobPermArgs& q);
+// the fallback's substitution: dst[r][g] = orig[src[r]][g] (src == nullptr: orig[r][g]);
+// codes [N][S] of code_bytes 1 / 2 / 4
+void launch_permute_column(hipStream_t st, void* dst, const void* orig, int code_bytes, int64_t N,
+                           int32_t S, int32_t g, const int32_t* src);
 // class-tile grouping of gini histogram entries (one workgroup per piece)
 // the grouping with known (segment, tile) sizes: cursors[q ntc + t] start at the tile's first
 // position and advance by atomics; pieces of tile_scatter_known_piece() entries

@@ -527,6 +527,30 @@ def oob_metrics(pred, n_oob, y, classification, metricName=None):
     return res
 
 
+def oob_permutation_importance(base_pred, perm_pred, n_oob, y, classification, metricName=None):
+    """Permutation importances from out-of-bag predictions (host arrays, numpy only):
+    {"metric", "baseline", "permuted" [K], "importance" [K]}.  baseline and permuted[k] are
+    the value of oob_metrics for base_pred and perm_pred[k] (rows with n_oob == 0 left out);
+    the importance of row k is how much the metric worsens: permuted[k] - baseline for rmse /
+    mse / mae, baseline - permuted[k] for accuracy / r2."""
+    perm_pred = np.asarray(perm_pred, np.float64)
+    if perm_pred.ndim != 2:
+        raise nat.IllegalArgumentException(nat.SBAG_EINVAL, "perm_pred must be [K, N]")
+    base = oob_metrics(base_pred, n_oob, y, classification, metricName)
+    permuted = np.array([oob_metrics(p, n_oob, y, classification, base["metric"])["value"] for p in perm_pred],
+                        np.float64).reshape(len(perm_pred))
+    higher_is_better = base["metric"] in ("accuracy", "r2")
+    importance = base["value"] - permuted if higher_is_better else permuted - base["value"]
+    return {"metric": base["metric"], "baseline": base["value"], "permuted": permuted,
+            "importance": importance}
+
+
+def permutation_source_rows(seed, repeat, feature, num_rows):
+    """The source rows `permutationImportances` uses for (repeat, feature): a permutation
+    of the rows drawn from numpy's default_rng([seed, repeat, feature])."""
+    return np.random.default_rng([seed, repeat, feature]).permutation(num_rows).astype(np.int32)
+
+
 class _BaggingModel(_BaggingParams):
     _agg = None
 
@@ -598,17 +622,7 @@ class _BaggingModel(_BaggingParams):
         counts them and pred[r] is NaN where there is none.  `dataset` is the Frame (its own
         partition_offsets are used) or the DeviceDataset (with `partition_offsets`) the
         model was fitted on."""
-        lb, le = self.learner_range or (0, self.numBaseModels)
-        if le - lb != self.numBaseModels:
-            raise nat.IllegalArgumentException(
-                nat.SBAG_EINVAL, f"learner range {(lb, le)} does not hold {self.numBaseModels} models")
-        if isinstance(dataset, nat.DeviceDataset):
-            ds, part, own = dataset, partition_offsets, False
-        else:
-            if not isinstance(dataset, Frame):
-                X, y = dataset
-                dataset = Frame(X, y, partition_offsets)
-            ds, part, own = dataset.device_dataset(nat.default_context(0)), dataset.partition_offsets, True
+        (lb, le), ds, part, own = self._oob_dataset(dataset, partition_offsets)
         try:
             return nat.predict_oob(ds.ctx, self.native_forest(), ds, replacement=self.get("replacement"),
                                    sample_ratio=self.get("sampleRatio"), seed=self.get("seed"),
@@ -617,6 +631,87 @@ class _BaggingModel(_BaggingParams):
         finally:
             if own:
                 ds.free()
+
+    def _oob_dataset(self, dataset, partition_offsets):
+        """(learner range, device dataset, partition offsets, dataset is ours to free) of the
+        out-of-bag calls."""
+        lb, le = self.learner_range or (0, self.numBaseModels)
+        if le - lb != self.numBaseModels:
+            raise nat.IllegalArgumentException(
+                nat.SBAG_EINVAL, f"learner range {(lb, le)} does not hold {self.numBaseModels} models")
+        if isinstance(dataset, nat.DeviceDataset):
+            return (lb, le), dataset, partition_offsets, False
+        if not isinstance(dataset, Frame):
+            X, y = dataset
+            dataset = Frame(X, y, partition_offsets)
+        return (lb, le), dataset.device_dataset(nat.default_context(0)), dataset.partition_offsets, True
+
+    def tested_features(self):
+        """The global feature indices some split of some tree tests (sorted)."""
+        used = set()
+        for sub, m in zip(self.subspaces, self.models):
+            inner = m.nodes["left"] >= 0
+            used.update(int(g) for g in np.asarray(sub)[m.nodes["feature"][inner]])
+        return sorted(used)
+
+    def permutationImportances(self, dataset, features=None, numRepeats=1, seed=0, metricName=None,
+                               partition_offsets=None):
+        """Breiman's permutation importances on the out-of-bag predictions of the training
+        data: how much the out-of-bag metric (oob_metrics) worsens when a feature's column is
+        replaced by a permutation of itself, the trees and bags unchanged.  `dataset` and
+        `partition_offsets` as in oobPredictions; `features` the global feature indices
+        (None: every feature of the dataset).  The source rows of (repeat p, feature j) are
+        permutation_source_rows(seed, p, j, N).  A feature no split tests has importance
+        exactly 0.0 (no device work).  Returns {"metric", "baseline", "features",
+        "importances" (mean over the repeats, summed in repeat order), "std", "perRepeat"
+        [numRepeats x len(features)]}."""
+        numRepeats = int(numRepeats)
+        if numRepeats < 1:
+            raise nat.IllegalArgumentException(nat.SBAG_EINVAL, "numRepeats must be >= 1")
+        (lb, le), ds, part, own = self._oob_dataset(dataset, partition_offsets)
+        try:
+            N, F = ds.shape[0], ds.shape[1]
+            feats = list(range(F)) if features is None else [int(j) for j in features]
+            for j in feats:
+                if not 0 <= j < F:
+                    raise nat.IllegalArgumentException(nat.SBAG_EINVAL, f"feature {j} is outside [0, {F})")
+            if isinstance(dataset, nat.DeviceDataset):
+                y = dataset.labels()
+            else:
+                y = dataset.label if isinstance(dataset, Frame) else dataset[1]
+            cls = self._agg == nat.AGG_MODE
+            kw = dict(replacement=self.get("replacement"), sample_ratio=self.get("sampleRatio"),
+                      seed=self.get("seed"), learner_begin=lb, learner_end=le, partition_offsets=part,
+                      agg=self._agg)
+            forest = self.native_forest()
+            tested = set(self.tested_features())
+            per = np.zeros((numRepeats, len(feats)), np.float64)
+            # (repeat, position) pairs that need the device, in groups whose host result
+            # (8 N bytes per slot, and 4 N of source rows) stays near 1 GB
+            todo = [(r, i) for r in range(numRepeats) for i, j in enumerate(feats) if j in tested]
+            group = max(1, int((1 << 30) // (12 * max(N, 1))))
+            baseline = None
+            for g0 in range(0, len(todo), group):
+                chunk = todo[g0:g0 + group]
+                src = np.stack([permutation_source_rows(seed, r, feats[i], N) for r, i in chunk])
+                perm, base, n_oob = nat.predict_oob_permuted(
+                    ds.ctx, forest, ds, features=[feats[i] for _, i in chunk], src_rows=src, **kw)
+                res = oob_permutation_importance(base, perm, n_oob, y, cls, metricName)
+                baseline = res
+                for (r, i), v in zip(chunk, res["importance"]):
+                    per[r, i] = v
+            if baseline is None:  # nothing to permute: the baseline alone
+                pred, n_oob = nat.predict_oob(ds.ctx, forest, ds, **kw)
+                m = oob_metrics(pred, n_oob, y, cls, metricName)
+                baseline = {"metric": m["metric"], "baseline": m["value"]}
+        finally:
+            if own:
+                ds.free()
+        total = np.zeros(len(feats), np.float64)
+        for r in range(numRepeats):
+            total = total + per[r]
+        return {"metric": baseline["metric"], "baseline": baseline["baseline"], "features": feats,
+                "importances": total / numRepeats, "std": per.std(axis=0), "perRepeat": per}
 
     def oobScore(self, dataset, metricName=None, partition_offsets=None):
         """The out-of-bag estimate of the model's error on its training data (oob_metrics of
