@@ -229,6 +229,11 @@ typedef struct {
                               node's run of pieces, caused by the packed word's entry limit
                               alone (0 unless one workgroup holds more than flush_limit
                               entries of a node; SBAG_HIST_FLUSH_LIMIT lowers the limit)    */
+  int64_t entry_capacity;  /* per-replica stride of the fit's two in-bag entry lists: the row
+                              count N (full lists), or the largest in-bag row count + 4096
+                              rounded up to 64, capped at N (tight lists: real-valued labels,
+                              lists past 40 % of the device, SBAG_ENT_TIGHT=1); the largest
+                              of the parts of a split learner range                         */
 } sbag_timing;
 int sbag_forest_timing(const sbag_forest* f, sbag_timing* out);
 

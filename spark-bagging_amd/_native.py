@@ -88,7 +88,7 @@ class Timing(ctypes.Structure):
         ("exact_fallbacks", ctypes.c_int64), ("hist_lds_atomics", ctypes.c_double),
         ("group_ms", ctypes.c_double), ("chain_ms", ctypes.c_double),
         ("root_ms", ctypes.c_double), ("root_mfma_ops", ctypes.c_double),
-        ("hist_midrun_flushes", ctypes.c_int64)]
+        ("hist_midrun_flushes", ctypes.c_int64), ("entry_capacity", ctypes.c_int64)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}

@@ -43,6 +43,7 @@
 #include <cstdlib>
 
 #include "sbag_internal.h"
+#include "sbag_psum_index.h"
 
 namespace sbag {
 
@@ -721,7 +722,7 @@ __global__ __launch_bounds__(64) void k_fb_chainx(F64BucketArgs A, int nchain) {
 // bins -- 48 ms; one run per wave, 4 predicated draws per entry -- ~4 ms per level; this
 // kernel -- 29 ms.)  k_fb_pmerge then adds the P partials of every (task, bin) in partition
 // order.
-constexpr int kPwU = 8;  // rounds of 64 entries per step
+constexpr int kPwU = kPsumRounds;  // rounds of 64 entries per step (sbag_psum_index.h)
 __global__ __launch_bounds__(256) void k_fb_runs(F64BucketArgs A, int64_t runs) {
   const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (g >= runs) return;
@@ -763,7 +764,7 @@ __global__ __launch_bounds__(256) void k_fb_psum(F64BucketArgs A, int64_t runs, 
   const uint16_t* rb[R];
   const double* ry[R];
   const uint64_t* re[R];
-  int32_t len[R], lm1[R];
+  int32_t len[R];
   int32_t steps = 0;
 #pragma unroll
   for (int r = 0; r < R; r++) {
@@ -779,7 +780,6 @@ __global__ __launch_bounds__(256) void k_fb_psum(F64BucketArgs A, int64_t runs, 
     ry[r] = kCarried ? A.ey_in + lo : nullptr;
     re[r] = A.ent_in + lo;
     len[r] = (int32_t)n;
-    lm1[r] = max((int32_t)n - 1, 0);
     steps = max(steps, (int32_t)((n + 64 * kRu - 1) / (64 * kRu)));
   }
   uint32_t* scnt = s_cnt[wv];
@@ -797,17 +797,26 @@ __global__ __launch_bounds__(256) void k_fb_psum(F64BucketArgs A, int64_t runs, 
   for (int32_t st = 0; st < steps; st++) {
     uint32_t kv[kPwU], rs[kPwU];
     double yv[kPwU];
-    // round u: run u / kRu, its entry st 64 kRu + 64 (u % kRu) + lane (loads at clamped
-    // offsets, unconditional: one memory latency per step)
+    // round u: run u / kRu, its entry st 64 kRu + 64 (u % kRu) + lane (psum_slot: loads at
+    // clamped offsets, unconditional inside a run: one memory latency per step.  An empty run
+    // -- wave-uniform -- loads nothing: its base is its task's end, for a replica's last node
+    // the end of the replica's entries, and what a lane past its run's end loaded is no entry
+    // of the run, so only a valid lane's row index gathers a label)
 #pragma unroll
     for (int u = 0; u < kPwU; u++) {
       const int r = u / kRu;
-      const int32_t i = min(st * 64 * kRu + 64 * (u % kRu) + lane, lm1[r]);
-      kv[u] = (uint32_t)rb[r][i];
-      if constexpr (kCarried)
-        yv[u] = ry[r][i];
-      else
-        yv[u] = A.y[(uint32_t)re[r][i]];
+      const PsumSlot s = psum_slot(st, u % kRu, lane, len[r], kRu);
+      kv[u] = 0u;
+      yv[u] = 0.0;
+      if (s.load >= 0) {
+        kv[u] = (uint32_t)rb[r][s.load];
+        if constexpr (kCarried) {
+          yv[u] = ry[r][s.load];
+        } else {
+          const uint64_t e = re[r][s.load];
+          if (s.valid) yv[u] = A.y[(uint32_t)e];
+        }
+      }
     }
     // ranks: the round's lanes of each key by an atomic OR of the lane bits into the key's
     // mask (the OR's result does not depend on the lanes' order), then the lanes before this
@@ -815,7 +824,7 @@ __global__ __launch_bounds__(256) void k_fb_psum(F64BucketArgs A, int64_t runs, 
 #pragma unroll
     for (int u = 0; u < kPwU; u++) {
       const int r = u / kRu;
-      const bool valid = st * 64 * kRu + 64 * (u % kRu) + lane < len[r];
+      const bool valid = psum_slot(st, u % kRu, lane, len[r], kRu).valid;
       const uint32_t key = valid ? ((uint32_t)r << nbits | (kv[u] & 0xffu)) : (uint32_t)kKeys;
       seq[key] = 0ull;
       __hip_atomic_fetch_or(&seq[key], me, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);

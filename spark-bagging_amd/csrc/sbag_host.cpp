@@ -1619,6 +1619,7 @@ static void merge_forests(sbag_forest* fa, sbag_forest* fb) {
   T.hist_lds_atomics += U.hist_lds_atomics;
   T.group_ms += U.group_ms;
   T.hist_midrun_flushes += U.hist_midrun_flushes;
+  T.entry_capacity = std::max(T.entry_capacity, U.entry_capacity);
 }
 
 // Two learner parts run side by side only when both workspaces fit the device next to what
@@ -2838,8 +2839,11 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
   int64_t cap = N;
   size_t dev_free0 = 0, dev_total0 = 0;
   (void)hipMemGetInfo(&dev_free0, &dev_total0);
-  static const int cap_env = getenv("SBAG_ENT_TIGHT") ? atoi(getenv("SBAG_ENT_TIGHT")) : -1;  // (A/B)
-  const bool tight = cap_env >= 0 ? cap_env != 0 : f64 || (double)R * N * 16.0 > 0.4 * (double)dev_total0;
+  // (SBAG_ENT_TIGHT=0/1, read per fit, overrides the 40 % rule on the integer path alone: the
+  // fp64 path's compaction needs the pre-count's offsets, Σ count and max count)
+  const char* cap_str = getenv("SBAG_ENT_TIGHT");
+  const int cap_env = cap_str ? atoi(cap_str) : -1;
+  const bool tight = f64 || (cap_env >= 0 ? cap_env != 0 : (double)R * N * 16.0 > 0.4 * (double)dev_total0);
   if (tight) {
     TRY(ws_typed(c, "inbag_ncnt", (size_t)R * nchunk, &d_ncnt));
     {
@@ -4151,6 +4155,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
     T.exact_fallbacks = G.fallbacks;
     T.hist_launches = hist_launches;
     T.hist_midrun_flushes = hist_midrun;
+    T.entry_capacity = cap;
     T.hist_alg_bytes = hist_alg_bytes;
     T.hist_entries = hist_entries;
     T.hist_lds_atomics = hist_lds;
@@ -4843,6 +4848,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
   T.exact_fallbacks = fallbacks;
   T.hist_launches = hist_launches;
   T.hist_midrun_flushes = hist_midrun;
+  T.entry_capacity = cap;
   T.hist_alg_bytes = hist_alg_bytes;
   T.hist_entries = hist_entries;
   T.hist_lds_atomics = hist_lds;

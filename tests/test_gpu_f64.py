@@ -110,6 +110,47 @@ def test_cpusmall_nondyadic_partitions_bit_exact(ctx, cpusmall, part, depth):
     assert (nat.predict(ctx, forest, X, nat.AGG_MEAN) == oracle.predict(orf, X)).all()
 
 
+def _forest_bytes(forest):
+    return [tuple(a.tobytes() for a in forest.tree(t)) for t in range(len(forest))]
+
+
+@pytest.mark.parametrize("part", [None, [0, 1000, 3000, 5000, 8192]], ids=["p1", "p4"])
+def test_ent_tight_knob_cannot_turn_off_the_fp64_precount(ctx, cpusmall, monkeypatch, part):
+    """SBAG_ENT_TIGHT=0 on real-valued labels: the fp64 engine's ordered compaction needs the
+    pre-count (its chunk offsets, and with them Σ count and the largest count), so the knob
+    -- read per fit -- is ignored there: the same forest as the default fit byte for byte, the
+    same entry capacity, bit-exact against the oracle."""
+    X, y = cpusmall
+    monkeypatch.delenv("SBAG_ENT_TIGHT", raising=False)
+    plain, orf = _fit_both(ctx, X, y * np.pi, 6, depth=6, part=part)
+    monkeypatch.setenv("SBAG_ENT_TIGHT", "0")
+    forest = _fit(ctx, X, y * np.pi, 6, 6, part)
+    tp, tf = plain.timing(), forest.timing()
+    assert tp["chain_ms"] > 0.0 and tf["chain_ms"] > 0.0, (tp, tf)
+    assert 0 < tf["entry_capacity"] == tp["entry_capacity"] <= len(y), (tp, tf)
+    assert _forest_bytes(forest) == _forest_bytes(plain)
+    assert_forest_equal(forest, orf)
+
+
+@pytest.mark.parametrize("part", [[0, 0, 4000, 4000, 8192], [round(i * 8192 / 64) for i in range(65)]],
+                         ids=["empty-partitions", "p64"])
+def test_labels_gathered_by_row_on_many_empty_runs(ctx, cpusmall, monkeypatch, part):
+    """SBAG_F64_NO_CARRY=1 (k_fb_psum gathers y[row] instead of reading labels carried beside
+    the entries) where most (node, partition) runs are empty or a few entries long: depth 10
+    over empty partitions and over 64 of them.  Bit-exact against the oracle and byte-equal
+    to the carried fit.  (What an empty run or a lane past its run's end may load is
+    psum_slot's rule, swept by tests/test_psum_index_host.py: those lanes are masked out of
+    every sum, so no output here can show them.)"""
+    X, y = cpusmall
+    monkeypatch.delenv("SBAG_F64_NO_CARRY", raising=False)
+    carried, orf = _fit_both(ctx, X, y * np.pi, 6, depth=10, part=part)
+    monkeypatch.setenv("SBAG_F64_NO_CARRY", "1")
+    forest = _fit(ctx, X, y * np.pi, 6, 10, part)
+    assert forest.timing()["chain_ms"] > 0.0
+    assert_forest_equal(forest, orf)
+    assert _forest_bytes(forest) == _forest_bytes(carried)
+
+
 def test_partition_order_is_visible(ctx, cpusmall):
     """The same bags fitted as 1 and as 4 partitions give different fp64 statistics (the
     merge order shows in the sums), each bit-exact against its own oracle run."""
