@@ -5140,10 +5140,12 @@ int sbag_predict(sbag_ctx* c, const sbag_forest* f, const double* X, int64_t N, 
     for (const sbag_node& n : t.nodes)
       if (n.left >= 0) T[t.sub[n.feature]].push_back(n.threshold);
   std::vector<int64_t> toff(F + 1, 0);
+  size_t max_thr = 0;
   for (int g = 0; g < F; g++) {
     std::sort(T[g].begin(), T[g].end());
     T[g].erase(std::unique(T[g].begin(), T[g].end()), T[g].end());
     toff[g + 1] = toff[g] + (int64_t)T[g].size();
+    max_thr = std::max(max_thr, T[g].size());
   }
   const int32_t Sq = (F + 15) / 16 * 16;
   PredictArgs pa{};
@@ -5151,7 +5153,9 @@ int sbag_predict(sbag_ctx* c, const sbag_forest* f, const double* X, int64_t N, 
   pa.S = Sq;
   pa.agg = agg;
   TiledPlan P;
-  const bool tiled = per_tree == nullptr &&
+  // (the codes are u16 and run to the feature's threshold count inclusive: a feature with
+  // more than 65535 distinct thresholds would wrap them, so such a forest takes the node walk)
+  const bool tiled = per_tree == nullptr && max_thr <= 65535 &&
                      plan_tiled(f, pa, F, [&](int g, double thr) {
                        return (int64_t)(std::lower_bound(T[g].begin(), T[g].end(), thr) - T[g].begin());
                      }, P);
