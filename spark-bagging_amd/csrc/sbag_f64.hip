@@ -29,6 +29,7 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "sbag_div.h"
 #include "sbag_internal.h"
 
 namespace sbag {
@@ -477,9 +478,9 @@ void launch_f64_hist(hipStream_t st, const F64HistArgs& a, int nnodes, int ngrou
 // ---------------------------------------------------------------- split (binsToBestSplit)
 namespace {
 __device__ __forceinline__ double var_impurity(double count, double sum, double sumsq) {
-  if (count == 0) return 0.0;  // Variance.calculate
-  const double squared_loss = sumsq - (sum * sum) / count;
-  return squared_loss / count;
+  if (count == 0) return 0.0;  // Variance.calculate (div_rn: subnormal quotients as IEEE rounds them)
+  const double squared_loss = sumsq - div_rn(sum * sum, count);
+  return div_rn(squared_loss, count);
 }
 constexpr double kMinValue = -1.7976931348623157e308;  // Double.MinValue
 }  // namespace

@@ -42,6 +42,7 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "sbag_div.h"
 #include "sbag_internal.h"
 #include "sbag_psum_index.h"
 
@@ -52,9 +53,9 @@ constexpr double kU = 1.1102230246251565e-16;          // 2^-53, unit roundoff
 constexpr double kMinValueS = -1.7976931348623157e308;  // Double.MinValue
 
 __device__ __forceinline__ double var_imp(double count, double sum, double sumsq) {
-  if (count == 0) return 0.0;  // Variance.calculate
-  const double squared_loss = sumsq - (sum * sum) / count;
-  return squared_loss / count;
+  if (count == 0) return 0.0;  // Variance.calculate (div_rn: subnormal quotients as IEEE rounds them)
+  const double squared_loss = sumsq - div_rn(sum * sum, count);
+  return div_rn(squared_loss, count);
 }
 
 // block-wide exclusive scan of one int per thread (256 threads); block total in *total

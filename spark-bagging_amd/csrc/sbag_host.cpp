@@ -1962,7 +1962,10 @@ struct F64sGrow {
   void* hist_root;        // level-0 integer histograms, slot = replica
   int64_t slot_words;     // Fmax * NB * 3
   unsigned int cmax;      // largest draw count of a row
-  double inv_scale, eps;  // the labels' fixed-point image: k 2^-s, |y - k 2^-s| <= eps
+  // the labels' fixed-point image: k 2^-s, |y - k 2^-s| <= eps, both in units of 2^yexp
+  // (2^yexp <= max|y| < 2^(yexp+1), 0 for all-zero labels): the screen works on y 2^-yexp
+  double inv_scale, eps;
+  int yexp;
   // integer (count, Σ c k) histograms of node segments of `ent` into slots of `hist`
   std::function<int(const std::vector<std::pair<int64_t, int64_t>>&, const std::vector<ParentInfo>&,
                     const uint64_t*, void*)> int_hist;
@@ -2011,8 +2014,49 @@ static int grow_f64s(F64sGrow& G, std::vector<std::vector<BtNode>>& trees) {
     TRY(ws_typed(c, "f64_poff", G.poff.size(), &d_poff));
     TRY(h2d(c, d_poff, G.poff.data(), G.poff.size()));
   }
+  // Overflow: with n draws of |y| <= M no sum of Spark's exceeds n M (1 + gamma_n) and no
+  // sum of squares or sum*sum exceeds its square, so nothing it computes overflows while
+  // n M <= 2^511.  Past that its variance can be inf or NaN, which no bound covers: refused.
+  {
+    double draws = 0.0;
+    for (int r = 0; r < R; r++) draws = std::max(draws, (double)G.inbag[R + r]);
+    if (!(draws * G.lab.ymax_abs <= 0x1p511)) {
+      char msg[256];
+      snprintf(msg, sizeof msg,
+               "regression labels too large in magnitude: max|y| = %.6g over %.0f draws, and (draws x max|y|)^2 "
+               "overflows a Double (served while draws x max|y| <= 2^511)", G.lab.ymax_abs, draws);
+      return fail(SBAG_EUNSUPPORTED, msg);
+    }
+  }
+  // The screen's error model.  Every fp64 operation of Spark's obeys
+  //   fl(a op b) = (a op b)(1 + d) + t,  |d| <= u = 2^-53,  |t| <= eta = 2^-1075,
+  // t = 0 for + and - (a subnormal sum is exact) and for results of 2^-1022 or more.  The
+  // relative parts give the terms in u below; they scale with the labels.  The absolute
+  // parts do not, so the whole model is stated for the labels y 2^-yexp (max|y| in [1, 2)),
+  // in which eta counts 2^(-1075 - 2 yexp): nothing for ordinary labels (there every
+  // quantity below is the unscaled one times an exact power of two, and the screen decides
+  // as it would unscaled), comparable to the u terms once y*y nears 2^-1022, and infinite
+  // -- every node flagged, the exact kernels alone -- from about max|y| < 2^-1050 down.
+  // Scaling also keeps the screen's own arithmetic (k_f64_screen, this function) clear of
+  // under- and overflow at every label magnitude.
+  //   A sum of squares of m rows: each y*y carries one t, so m eta.  A candidate's left
+  //   sums are a prefix of the node's own bins (<= nl eta), its right sums total - left
+  //   (<= (n + nl) eta).  Variance.calculate: (sumSq - sum*sum/c)/c adds one t per product
+  //   and quotient: impurity_L within (nl + 2)/nl + 1 <= 4 eta, weighted impurity_R within
+  //   ((n + nl + 2)/nr + 1) nr/n <= 4 eta, the two weighted products one t each: a
+  //   candidate's gain carries at most 10 eta besides the parent's impurity; dn takes 16.
+  //   The parent's calculator: at the root left + right of one candidate, <= 3 n eta in
+  //   sumSq; below, a child's sums of its parent's chosen split, <= 2 n_parent eta (e2
+  //   carries them); its impurity adds 3 eta (dp).
   const double u = std::ldexp(1.0, -53);
-  const double M1 = G.lab.ymax_abs, M2 = G.lab.ymax_sq, Msq = std::max(M2, M1 * M1);
+  const double eta = std::ldexp(1.0, -1075 - 2 * G.yexp);  // (inf and 0 are both meant)
+  const double M1 = std::ldexp(G.lab.ymax_abs, -G.yexp), M2 = M1 * M1, Msq = M2;
+  // minInfoGain in the same units, rounded up where the scaling is not exact
+  double min_gain_s = G.tp.min_info_gain;
+  if (min_gain_s > 0.0) {
+    min_gain_s = std::ldexp(G.tp.min_info_gain, -2 * G.yexp);
+    if (std::ldexp(min_gain_s, 2 * G.yexp) != G.tp.min_info_gain) min_gain_s = std::nextafter(min_gain_s, INFINITY);
+  }
   // gamma_K of a node of n draws (inf when K u >= 1: every screen then flags)
   auto gam = [&](double n) {
     const double k = (n + NB + 2.0) * u;
@@ -2030,7 +2074,8 @@ static int grow_f64s(F64sGrow& G, std::vector<std::vector<BtNode>>& trees) {
     const double n = (double)G.inbag[R + r];
     // root: Spark's parent stats l0 + (total - l0) of the first feature with splits
     const double e = (2.0 * gam(n) + 4.0 * u) * 1.01 * n;
-    cur.push_back(LNode{r, 0, (int64_t)r * cap, (int64_t)r * cap + (int64_t)G.inbag[r], n, e * M1, e * M2});
+    cur.push_back(LNode{r, 0, (int64_t)r * cap, (int64_t)r * cap + (int64_t)G.inbag[r], n, e * M1,
+                        e * M2 + 3.0 * n * eta});
   }
   std::vector<int> f0(R, -1);  // first local feature with splits
   for (int r = 0; r < R; r++)
@@ -2066,8 +2111,14 @@ static int grow_f64s(F64sGrow& G, std::vector<std::vector<BtNode>>& trees) {
       for (int i = 0; i < M; i++) {
         h_slot_r[i] = cur[i].r;
         const double n = cur[i].n, g = gam(n);
-        hdn[i] = (7.0 * g + 30.0 * u + 4.0 * (g + u) * (g + u) * n) * Msq * 1.01;
-        hdp[i] = (cur[i].e2 / n + cur[i].e1 * (2.0 * n * M1 + cur[i].e1) / (n * n) + 8.0 * u * Msq) * 1.01;
+        // dn: a candidate's gain against its exact-arithmetic value, the parent's impurity
+        // apart: the summation and formula roundings, relative to max y^2, and 16 eta of
+        // underflow (derived above: <= 10 eta whatever n, the sums being divided by the
+        // counts).  dp: the parent's impurity, from its calculator's error bounds e1, e2 (e2
+        // with its rows' eta) and the formula's rounding and 3 eta.
+        hdn[i] = (7.0 * g + 30.0 * u + 4.0 * (g + u) * (g + u) * n) * Msq * 1.01 + 16.0 * eta;
+        hdp[i] = (cur[i].e2 / n + cur[i].e1 * (2.0 * n * M1 + cur[i].e1) / (n * n) + 8.0 * u * Msq) * 1.01 +
+                 3.0 * eta;
       }
       int32_t* d_slot_r;
       double *d_dn, *d_dp;
@@ -2087,7 +2138,7 @@ static int grow_f64s(F64sGrow& G, std::vector<std::vector<BtNode>>& trees) {
       sa.Fmax = Fmax;
       sa.NB = NB;
       sa.min_inst = G.tp.min_instances_per_node;
-      sa.min_gain = G.tp.min_info_gain;
+      sa.min_gain = min_gain_s;
       sa.inv_scale = G.inv_scale;
       sa.eps = G.eps;
       sa.dnode = d_dn;
@@ -2624,15 +2675,16 @@ static int grow_f64s(F64sGrow& G, std::vector<std::vector<BtNode>>& trees) {
       const double g = gam(q.n);
       const double nl = L.calc[0], nr = Rn.calc[0];
       const double el = g * nl * 1.01, er = 2.0 * (g + u) * (1.0 + g) * q.n * 1.01;
+      const double ce = 2.0 * q.n * eta;  // the children's sums of squares: this node's rows' underflow
       int sl = -1, sr = -1;
       if (!L.is_leaf) {
         sl = (int)next.size();
-        next.push_back(LNode{r, li, q.a, m, nl, el * M1, el * M2});
+        next.push_back(LNode{r, li, q.a, m, nl, el * M1, el * M2 + ce});
         nseg.push_back({q.a, m});
       }
       if (!Rn.is_leaf) {
         sr = (int)next.size();
-        next.push_back(LNode{r, li + 1, m, q.b, nr, er * M1, er * M2});
+        next.push_back(LNode{r, li + 1, m, q.b, nr, er * M1, er * M2 + ce});
         nseg.push_back({m, q.b});
       }
       // the smaller (or only) child is histogrammed, its sibling is parent - small
@@ -4094,10 +4146,11 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
   if (f64) {
     // the integer histograms of the labels' fixed-point image (exact when the labels are
     // dyadic, SBAG_F64=1) screen the splits; Spark's row-order fp64 sums give the stats
+    const int yexp = lab.ymax_abs > 0.0 ? std::ilogb(lab.ymax_abs) : 0;
     F64sGrow G{c, ds, lab, tp, R, N, Fmax, NB, S, h_Fr, h_nbins, thr, d_bins, bins_rstride, d_pos, d_Fr,
                d_nbins, h_pos, d_cols, cols_rstride, npad, entA, entB, cap, inbag, tm, hist_cur,
-               slot_words, cmax, std::ldexp(1.0, -lshift),
-               lab.label_ok ? 0.0 : std::ldexp(1.0, -lshift - 1),
+               slot_words, cmax, std::ldexp(1.0, -lshift - yexp),
+               lab.label_ok ? 0.0 : std::ldexp(1.0, -lshift - 1 - yexp), yexp,
                [&](const std::vector<std::pair<int64_t, int64_t>>& segs, const std::vector<ParentInfo>& par,
                    const uint64_t* ent, void* hist) -> int {
                  ha.ent_in = ent;
