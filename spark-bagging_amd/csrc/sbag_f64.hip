@@ -180,10 +180,9 @@ __global__ __launch_bounds__(256) void k_chunk_scan(const uint32_t* __restrict__
   if (threadIdx.x == 0) cursor[r] = carry;
 }
 
-// one entry per in-bag row, in row order.  STG: the block's entries of an iteration (and
+// one entry per in-bag row, in row order.  The block's entries of an iteration (and
 // their labels), contiguous in the output, are staged in LDS and stored by consecutive
 // threads, instead of each thread's up to 4 entries at its own scattered positions
-template <bool STG>
 __global__ __launch_bounds__(256) void k_compact_ordered(const uint8_t* __restrict__ counts,
                                                          const int32_t* __restrict__ labk, int64_t N,
                                                          int R, int64_t chunks,
@@ -198,8 +197,8 @@ __global__ __launch_bounds__(256) void k_compact_ordered(const uint8_t* __restri
   uint64_t* er = ent + (int64_t)r * cap;
   double* eyr = ey ? ey + (int64_t)r * cap : nullptr;  // (the carried fp64 labels, same positions)
   unsigned long long pos0 = base[(int64_t)r * chunks + chunk];
-  __shared__ uint64_t s_e[STG ? 1024 : 1];
-  __shared__ double s_y[STG ? 1024 : 1];
+  __shared__ uint64_t s_e[1024];
+  __shared__ double s_y[1024];
   const bool vec = ((N | (int64_t)(uintptr_t)cr) & 3) == 0;
   for (int it = 0; it < kChunkRows / 1024; it++) {
     const int64_t row0 = chunk * kChunkRows + (int64_t)it * 1024 + (int64_t)threadIdx.x * 4;
@@ -217,29 +216,19 @@ __global__ __launch_bounds__(256) void k_compact_ordered(const uint8_t* __restri
     for (int j = 0; j < 4; j++) n += c[j] ? 1 : 0;
     int tot;
     const int ex = block_excl_scan256(n, s_wave, &tot);
-    if (STG) {
-      int lp = ex;
+    int lp = ex;
 #pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (c[j]) {
-          if (eyr) s_y[lp] = y[row0 + j];
-          s_e[lp++] = pack_entry((uint32_t)(row0 + j), labk[row0 + j], c[j]);
-        }
-      block_sync();
-      for (int q = threadIdx.x; q < tot; q += 256) {
-        er[pos0 + q] = s_e[q];
-        if (eyr) eyr[pos0 + q] = s_y[q];
+    for (int j = 0; j < 4; j++)
+      if (c[j]) {
+        if (eyr) s_y[lp] = y[row0 + j];
+        s_e[lp++] = pack_entry((uint32_t)(row0 + j), labk[row0 + j], c[j]);
       }
-      block_sync();  // (the staging is rewritten by the next iteration)
-    } else {
-      unsigned long long pos = pos0 + (unsigned long long)ex;
-#pragma unroll
-      for (int j = 0; j < 4; j++)
-        if (c[j]) {
-          if (eyr) eyr[pos] = y[row0 + j];
-          er[pos++] = pack_entry((uint32_t)(row0 + j), labk[row0 + j], c[j]);
-        }
+    block_sync();
+    for (int q = threadIdx.x; q < tot; q += 256) {
+      er[pos0 + q] = s_e[q];
+      if (eyr) eyr[pos0 + q] = s_y[q];
     }
+    block_sync();  // (the staging is rewritten by the next iteration)
     pos0 += (unsigned long long)tot;
   }
 }
@@ -257,13 +246,8 @@ void launch_compact_ordered(hipStream_t st, const uint8_t* counts, const int32_t
                             double* ey) {
   const int64_t chunks = compact_ordered_chunks(N);
   hipLaunchKernelGGL(k_chunk_scan, dim3(R), dim3(256), 0, st, d_ncnt, chunks, d_base, d_cursor);
-  static const bool stg = !getenv("SBAG_COMPACT_STG") || atoi(getenv("SBAG_COMPACT_STG")) != 0;  // (A/B)
-  if (stg)
-    hipLaunchKernelGGL(k_compact_ordered<true>, dim3((unsigned)(chunks * R)), dim3(256), 0, st, counts, labk,
-                       N, R, chunks, d_base, ent, cap, y, ey);
-  else
-    hipLaunchKernelGGL(k_compact_ordered<false>, dim3((unsigned)(chunks * R)), dim3(256), 0, st, counts, labk,
-                       N, R, chunks, d_base, ent, cap, y, ey);
+  hipLaunchKernelGGL(k_compact_ordered, dim3((unsigned)(chunks * R)), dim3(256), 0, st, counts, labk, N, R,
+                     chunks, d_base, ent, cap, y, ey);
 }
 
 int64_t compact_ordered_chunks(int64_t N) { return (N + kChunkRows - 1) / kChunkRows; }

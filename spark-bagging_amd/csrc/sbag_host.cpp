@@ -1447,9 +1447,7 @@ static bool hist_geometry(int S, int Fmax, int NB, int NS, bool gini_layout, His
   g.lds = lds_for(g.FT, ct);
   g.rl = 0;
   // row lanes when they carry fewer dump lanes than 64-feature lane groups
-  // (SBAG_HIST_RL_FORCE=1: whenever the layout allows them, for A/B)
-  static const bool rl_force = getenv("SBAG_HIST_RL_FORCE") && atoi(getenv("SBAG_HIST_RL_FORCE")) != 0;
-  if (rl_mode && (rl_force || roundup(g.FT, hist_rl_lanes()) < roundup(g.FT, 64))) {
+  if (rl_mode && roundup(g.FT, hist_rl_lanes()) < roundup(g.FT, 64)) {
     const size_t b = hist_rl_lds_bytes(NB, ct, g.FPH, gini_layout);
     if (b <= hard) {
       g.rl = rl_mode;
@@ -1510,7 +1508,7 @@ static void build_work(const std::vector<std::pair<int64_t, int64_t>>& segs, int
 // Flushes of one histogram launch that flush_limit alone causes (sbag_timing.
 // hist_midrun_flushes): each workgroup's piece range walked with the kernels' own rule --
 // k_hist and k_hist_rl flush before a piece when `slot != cur_slot || tile != cur_tile ||
-// acc + (b - a) > A.flush_limit` (sbag_kernels.hip:1358 in k_hist's piece loop and :1632 in
+// acc + (b - a) > A.flush_limit` (in k_hist's piece loop and in
 // k_hist_rl's; a change to either rule belongs here too) -- and only the flushes of the last
 // clause counted.  Pieces must carry their parents' slot and
 // tile (upload_work); `grouped` as HistArgs.grouped (else every tile is 0).  Counted once per
@@ -1670,8 +1668,7 @@ static int fit_learners(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* fp
       // the estimate had missed the last one)
       const bool force_f64 = getenv("SBAG_F64") && atoi(getenv("SBAG_F64")) != 0;
       const bool gini = fp->tree.impurity == SBAG_IMPURITY_GINI;
-      bool ranked = (gini || (ds->lab.label_ok && !force_f64)) &&
-                    (!getenv("SBAG_BIN_RANKED") || atoi(getenv("SBAG_BIN_RANKED")) != 0);
+      bool ranked = gini || (ds->lab.label_ok && !force_f64);
       const double ratio = fp->sampler.sample_ratio;
       const double frac = std::min(1.0, (fp->sampler.replacement ? 1.0 - std::exp(-ratio) : ratio) * 1.02 + 1e-3);
       const double sratio = fp->subspace_bug_compat ? fp->sampler.sample_ratio : fp->subspace_ratio;
@@ -2152,8 +2149,7 @@ static int grow_f64s(F64sGrow& G, std::vector<std::vector<BtNode>>& trees) {
       HIP_TRY(hipGetLastError());
       G.tm.end(h);
       TRY(d2h(c, so.data(), d_so, (size_t)M));
-      const bool all_features = getenv("SBAG_F64_FALLBACK_ALL") != nullptr;  // (A/B, tests)
-      if (!all_features) TRY(d2h(c, cmask.data(), d_cm, cmask.size()));
+      TRY(d2h(c, cmask.data(), d_cm, cmask.size()));
     }
     // ... and the first feature with splits of the node's replica (at the root its bins
     // give Spark's parent stats; a node without any valid candidate takes its first split)
@@ -2363,8 +2359,7 @@ static int grow_f64s(F64sGrow& G, std::vector<std::vector<BtNode>>& trees) {
       TRY(h2d(c, d_chain, chain.data(), (size_t)A));
       int h = G.tm.begin(T_FIX);
       if (walk_fallback) {  // the row-order walk of every feature
-        const int fpw_env = getenv("SBAG_F64_FPW") ? atoi(getenv("SBAG_F64_FPW")) : 64;
-        const int FPW = std::max(1, std::min(f64_hist_width(NB), fpw_env));
+        const int FPW = f64_hist_width(NB);  // (64 or 32: never above the 64 lanes of a wave)
         const int ngroups = (Fmax + 1 + FPW - 1) / FPW;
         const int parts = (int64_t)A * ngroups < 1024 ? 2 : 1;
         F64HistArgs ha{};
@@ -2532,11 +2527,9 @@ static int grow_f64s(F64sGrow& G, std::vector<std::vector<BtNode>>& trees) {
     const int nchain1 = (int)tasks[1].size();
     std::vector<F64SplitOut> fo(fin.size());
     std::vector<int64_t> nleft;
-    double* dbg_chist = nullptr;  // (SBAG_F64_DEBUG: the chain histograms, for a violation report)
     if (!tasks[0].empty()) {
       double* d_chist;
       TRY(ws_typed(c, "fb_chist", (size_t)std::max(1, nchain0 + nchain1) * NB * 3, &d_chist));
-      dbg_chist = d_chist;
       int h = G.tm.begin(T_CHAIN);
       // one launch sequence for both passes: the root's chains of the chosen features and of
       // the first features run side by side (the root has few, long chains: 2 x 2048 per C3
@@ -2615,29 +2608,8 @@ static int grow_f64s(F64sGrow& G, std::vector<std::vector<BtNode>>& trees) {
       const LNode& q = cur[i];
       const bool decided = !so[i].flag;
       const F64SplitOut& o = decided ? fo[fin_of[i]] : xo[xi[i]];
-      if (decided && (o.s != so[i].s || !o.valid || !(o.gain > 0.0) || o.gain < G.tp.min_info_gain)) {
-        if (getenv("SBAG_F64_DEBUG")) {
-          fprintf(stderr,
-                  "[sbag] screen violation level %d slot %d r %d entries %lld: screen f %d s %d gain %.17g margin "
-                  "%.17g | exact f %d s %d gain %.17g valid %d | min_gain %.17g | node calc %.17g %.17g %.17g\n",
-                  level, i, q.r, (long long)(q.b - q.a), so[i].f, so[i].s, so[i].gain, so[i].margin, o.f, o.s,
-                  o.gain, o.valid, G.tp.min_info_gain, trees[q.r][q.node].calc[0], trees[q.r][q.node].calc[1],
-                  trees[q.r][q.node].calc[2]);
-          std::vector<uint64_t> ih((size_t)NB * 3);
-          (void)d2h(c, ih.data(), (const uint64_t*)hist_cur + ((size_t)i * Fmax + so[i].f) * NB * 3, ih.size());
-          std::vector<double> ch((size_t)NB * 3, 0.0);
-          if (dbg_chist) (void)d2h(c, ch.data(), dbg_chist + (size_t)fin[fin_of[i]].t * NB * 3, ch.size());
-          const F64FinishNode& fnd = fin[fin_of[i]];
-          fprintf(stderr, "[sbag]   finish t %d f %d s %d nsp %d set %d impurity %.17g calc %.17g %.17g %.17g NB %d\n",
-                  fnd.t, fnd.f, fnd.s, fnd.nsp, fnd.ch.set, fnd.ch.impurity, fnd.ch.calc[0], fnd.ch.calc[1],
-                  fnd.ch.calc[2], NB);
-          for (int b = 0; b < NB; b++)
-            if (ih[b * 3] || ch[b * 3] != 0.0)
-              fprintf(stderr, "[sbag]   bin %d: int count %llu sck %lld | chain %.17g %.17g %.17g\n", b,
-                      (unsigned long long)ih[b * 3], (long long)ih[b * 3 + 1], ch[b * 3], ch[b * 3 + 1], ch[b * 3 + 2]);
-        }
+      if (decided && (o.s != so[i].s || !o.valid || !(o.gain > 0.0) || o.gain < G.tp.min_info_gain))
         return fail(SBAG_EDEVICE, "internal: the fp64 screen's split is not Spark's (bound violated)");
-      }
       const int r = q.r;
       {
         BtNode& n = trees[r][q.node];
@@ -2727,7 +2699,7 @@ static int grow_f64s(F64sGrow& G, std::vector<std::vector<BtNode>>& trees) {
       TRY(ws_typed(c, "triples", triples.size(), &d_tri));
       TRY(h2d(c, d_tri, triples.data(), triples.size()));
       int h = G.tm.begin(T_SUB);
-      launch_subtract(c->stream, hist_nxt, hist_cur, d_tri, (int)triples.size() / 3, G.slot_words, false);
+      launch_subtract(c->stream, hist_nxt, hist_cur, d_tri, (int)triples.size() / 3, G.slot_words);
       HIP_TRY(hipGetLastError());
       G.tm.end(h);
     }
@@ -3090,7 +3062,6 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
   double root_mfma_ops = 0;  // int8 MFMA operations of the root histogram (0: k_hist_rl)
   static const bool trace = getenv("SBAG_LEVEL_TRACE") != nullptr;
   int trace_level = -1;
-  static const bool group_off = getenv("SBAG_NO_TILE_GROUPING") != nullptr;
   std::vector<std::pair<int64_t, int64_t>> gsegs;
   std::vector<ParentInfo> gpar;
   // the last grouping's per-segment tile bounds [segs][ntc + 1], its class tile and buffer
@@ -3231,7 +3202,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
   };
   // class tiles of a gini histogram: group the entries by tile (k_hist only)
   auto maybe_grouped = [&](HistGeom& g, int S_, int NB_) -> int {
-    if (!gini || g.CT >= NS || g.rl || group_off) return SBAG_OK;
+    if (!gini || g.CT >= NS || g.rl) return SBAG_OK;
     HistGeom gg;
     if (hist_geometry(S_, Fmax, NB_, NS, true, gg, 0, true) && gg.CT < NS) {
       gg.grouped = true;
@@ -3260,9 +3231,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
                     const std::vector<ParentInfo>& par_in) -> int {
     const bool grouped = g.grouped && mode == kHistGini && !ha.count_only;
     // 16 waves per CU (two 512-thread workgroups), 32 for grouped class tiles
-    static const int wpc_env = getenv("SBAG_HIST_WPC") ? atoi(getenv("SBAG_HIST_WPC")) : 0;
-    const int wpc = std::max(1, std::min(wpc_env > 0 ? wpc_env : (grouped ? 4 : 2),
-                                         (int)((160 * 1024) / g.lds)));
+    const int wpc = std::max(1, std::min(grouped ? 4 : 2, (int)((160 * 1024) / g.lds)));
     const uint64_t* ent_saved = ha.ent_in;
     int ntiles = g.ntiles;
     double lt0 = hprof ? hnow() : 0.0;
@@ -3282,10 +3251,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
       lt0 = t;
     }
     ha.grouped = grouped ? 1 : 0;
-    // k_hist gathers aligned 4-byte words (SBAG_HIST_GW=1: single bytes, as before round 2e;
-    // 8-byte words were slower on C5, 134 vs 98 ms per fit)
-    static const int hist_gw = getenv("SBAG_HIST_GW") ? atoi(getenv("SBAG_HIST_GW")) : 4;
-    ha.dw = hist_gw == 1 ? 1 : 4;
+    // k_hist gathers aligned 4-byte words (8-byte words were slower on C5, 134 vs 98 ms per fit)
     // k_hist_rl row prefetch distance in passes of 4 entries (C3, ms per fit: 2 -> hist 92.1,
     // 3 -> 90.2 and step 134, 4 -> hist 89.7 and step 130, 5 -> flat); only 4 is built
     ha.rlpd = 4;
@@ -3294,9 +3260,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
     const std::vector<ParentInfo>& par = regrouped ? gpar : par_in;
     build_work(segs, flush_limit, 256 * wpc * (grouped ? 2 : 1), g.T, work);
     TRY(upload_work(par));
-    static const bool zplan_off = getenv("SBAG_ZERO_ALL") && atoi(getenv("SBAG_ZERO_ALL")) != 0;  // (A/B)
-    zplan = regrouped && mode == kHistGini && !zplan_off && ha.hct == g.CT && g.CT < NS && NS % g.CT == 0 &&
-            NS / g.CT <= 64;
+    zplan = regrouped && mode == kHistGini && ha.hct == g.CT && g.CT < NS && NS % g.CT == 0 && NS / g.CT <= 64;
     static const bool ztrace = getenv("SBAG_LEVEL_TRACE") != nullptr;
     if (ztrace)
       fprintf(stderr, "[sbag] zero plan %d (CT %d, layout tile %d, pieces %zu)\n", zplan ? 1 : 0, g.CT, ha.hct,
@@ -3324,12 +3288,9 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
     ha.wg_piece = d_wg;
     ha.parents = nullptr;
     // short (node, class tile) sub-segments (deep gini levels): the 256-thread k_hist with
-    // 32-entry gather groups; SBAG_HIST_SMALL = mean entries per sub-segment below which it
-    // is used (0: never)
-    static const double small_seg =
-        getenv("SBAG_HIST_SMALL") ? atof(getenv("SBAG_HIST_SMALL")) : 4096.0;
-    ha.small = (grouped && !segs.empty() && work.entries < small_seg * (double)segs.size()) ? 1 : 0;
-    ha.ablate = 0;
+    // 32-entry gather groups, below kSmallSeg mean entries per sub-segment
+    constexpr double kSmallSeg = 4096.0;
+    ha.small = (grouped && !segs.empty() && work.entries < kSmallSeg * (double)segs.size()) ? 1 : 0;
     ha.FT = g.FT;
     ha.FPH = g.FPH;
     ha.CT = g.CT;
@@ -3353,26 +3314,6 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
                       "limit flushes %lld (%lld after a store) zero plan %d\n",
               trace_level, cat, mode, grouped ? 1 : 0, segs.size(), (long long)ne, work.pieces.size(),
               work.nwg, ms, (long long)mid, (long long)mid_stored, zplan ? 1 : 0);
-    }
-    if (trace && getenv("SBAG_HIST_ABLATE")) {
-      // diagnostics: relaunch the same histogram with phases skipped (flushes always
-      // skipped, so the real result stays intact) and time each relaunch
-      for (int m : {1, 1 | 2, 1 | 4, 1 | 8, 1 | 2 | 4 | 8}) {
-        hipEvent_t e0, e1;
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        ha.ablate = m;
-        (void)hipEventRecord(e0, c->stream);
-        launch_hist(c->stream, ha, work.nwg, ntiles, mode, g.lds);
-        (void)hipEventRecord(e1, c->stream);
-        (void)hipEventSynchronize(e1);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        fprintf(stderr, "[sbag] ablate level %d mode %d ms %.3f\n", trace_level, m, ms);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-      }
-      ha.ablate = 0;
     }
     ha.ent_in = ent_saved;
     ha.grouped = 0;
@@ -3681,7 +3622,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
       HIP_TRY(hipGetLastError());
       tm.end(h);
       const bool splits_host = getenv("SBAG_SPLITS_HOST") && atoi(getenv("SBAG_SPLITS_HOST")) != 0;
-      if (!wide && !splits_host && !getenv("SBAG_DEBUG_SAMPLE") && ds->d_dict) {
+      if (!wide && !splits_host && ds->d_dict) {
         std::vector<int64_t> knw(reps.size()), kns(reps.size());
         for (size_t k = 0; k < reps.size(); k++) {
           const int r = reps[k];
@@ -3751,15 +3692,6 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
       if (!dev_splits) {
         vcs.assign((size_t)std::max<int64_t>(vc_total, 1), 0);
         TRY(d2h(c, vcs.data(), d_vcs, vcs.size()));
-      }
-      if (getenv("SBAG_DEBUG_SAMPLE")) {
-        for (int r : reps) {
-          int64_t tot = 0;
-          for (int64_t k = vcoff[(size_t)r * Fmax]; k < vcoff[(size_t)r * Fmax + 1]; k++) tot += vcs[k];
-          fprintf(stderr, "split sample r=%d n=%lld frac=%.17g sampled=%lld seed=%lld pst0=%llx\n", r,
-                  (long long)nw[r], sfrac[r], (long long)tot, (long long)tp.seed,
-                  (unsigned long long)pst[0]);
-        }
       }
     }
   }
@@ -3981,9 +3913,8 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
     } else {
       S = row_stride(Fmax);
       // integer labels: only the in-bag rows are binned, by rank (k_bin_ranked; the entries then
-      // carry ranks).  SBAG_BIN_RANKED=0: every row (k_bin_cuts)
-      const bool ranked = !f64 && (!getenv("SBAG_BIN_RANKED") || atoi(getenv("SBAG_BIN_RANKED")) != 0) &&
-                          bin_ranked_fits(ds->code_bytes, ds->S, S, Fmax, ncp);
+      // carry ranks); the fp64 engine bins every row (k_bin_cuts)
+      const bool ranked = !f64 && bin_ranked_fits(ds->code_bytes, ds->S, S, Fmax, ncp);
       int64_t capb = 0;
       for (int r = 0; r < R; r++) capb = std::max<int64_t>(capb, (int64_t)inbag[r]);
       const int64_t rows_b = ranked ? (capb + 1 + 63) / 64 * 64 : N;  // (room for the zero rows)
@@ -4011,8 +3942,6 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
         uint8_t* d_c;
         const int64_t npad_c = (rows_b + 127) / 128 * 128;
         TRY(ws_typed(c, "cols", (size_t)R * ncol_r * npad_c, &d_c));
-        // (SBAG_BIN_NO_COLS=1: the column copy by k_transpose afterwards, A/B)
-        static const bool no_cols = getenv("SBAG_BIN_NO_COLS") != nullptr;
         if (ranked) {
           if (!launch_bin_ranked(c->stream, ds->d_codes, ds->code_bytes, ds->S, entA, cap, d_inbag, capb, d_sub, d_Fr,
                                  Fmax, R, d_cut, ncp, d_z0, d_b, S, rows_b * S, d_c, ncol_r, npad_c,
@@ -4023,7 +3952,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
           cols_direct = d_c;
           cols_direct_npad = npad_c;
         } else if (launch_bin_cuts(c->stream, ds->d_codes, ds->code_bytes, N, ds->S, d_sub, d_Fr, Fmax, R, d_cut,
-                                   ncp, d_z0, d_b, S, (int64_t)N * S, no_cols ? nullptr : d_c, ncol_r, npad_c,
+                                   ncp, d_z0, d_b, S, (int64_t)N * S, d_c, ncol_r, npad_c,
                                    (int64_t)ncol_r * npad_c)) {
           cols_direct = d_c;
           cols_direct_npad = npad_c;
@@ -4051,8 +3980,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
     // per fit at levels with >= 1024 parents.
     auto planes_fit = [&](int nc, int nsp) {
       static const double cap_gb = getenv("SBAG_PLANES_MAX_GB") ? atof(getenv("SBAG_PLANES_MAX_GB")) : 24.0;
-      return nsp >= 1 && (double)nc * nsp * plane_nw32 * 4 <= cap_gb * (1ull << 30) &&
-             !getenv("SBAG_NO_PLANES");
+      return nsp >= 1 && (double)nc * nsp * plane_nw32 * 4 <= cap_gb * (1ull << 30);
     };
     if (identity && !getenv("SBAG_NO_LAYOUT_CACHE")) {
       // the codes are the bins: every column of every feature, once per dataset
@@ -4232,7 +4160,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
   // the per-level grouping (18.9 -> 4.1 ms per fit) but the partition's (node, tile) pieces
   // cost as much (25.7 -> 40.2 ms) and their host setup more (serialized fit 181 -> 223 ms).
   const bool tile_res_env = getenv("SBAG_TILE_RESIDENT") && atoi(getenv("SBAG_TILE_RESIDENT")) != 0;
-  const bool tile_res = tile_res_env && gini && g.grouped && !group_off &&
+  const bool tile_res = tile_res_env && gini && g.grouped &&
                         gtile_ent != nullptr && gtile_ct == g.CT &&
                         gtile_bounds.size() == (size_t)R * (ntc_t + 1);
   std::vector<std::pair<int64_t, int64_t>> tseg;  // [slot][ntc_t] sub-segments (tile_res)
@@ -4247,8 +4175,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
   }
   std::string hist_nxt_name = "histB", hist_cur_name = "histA";
   // gini: the larger children's histograms are derived (parent - smaller child) inside the next
-  // level's split search (k_split_gini), not by k_subtract; SBAG_NO_FUSED_SUB=1: k_subtract
-  static const bool fused_sub = !getenv("SBAG_NO_FUSED_SUB");
+  // level's split search (k_split_gini), not by k_subtract
   void* hist_prev = nullptr;        // the previous level's histograms (the derived slots' parents)
   std::vector<int32_t> derive;      // [2 slot] (parent slot, smaller-child slot) or -1
   int levels = 0;
@@ -4291,7 +4218,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
     sa.out = d_sout;
     sa.stats = d_sstats;
     sa.plane = (int64_t)M * NS;
-    if (gini && fused_sub && !derive.empty()) {
+    if (gini && !derive.empty()) {
       int32_t* d_der;
       TRY(ws_typed(c, "derive", derive.size(), &d_der));
       TRY(h2d(c, d_der, derive.data(), derive.size()));
@@ -4513,14 +4440,12 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
       // 8192 entries interleaved round-robin across the parents of a group, so the
       // concurrent workgroups spread over the group's cursors while the GPU reads
       // one column
-      static const int64_t piece =
-          getenv("SBAG_PART_PIECE") ? std::max<int64_t>(1024, atoll(getenv("SBAG_PART_PIECE"))) : 8192;
+      constexpr int64_t piece = 8192;
       // the gathered object: a side-bit plane (column, split) once parents are many (with
       // few parents, finer groups would crowd the workgroups onto fewer cursors), else a
       // column byte array.  Crossover measured at 128-256 parents (C5 level 3 / 4: cols
       // 2.21 / 2.49 ms, planes 2.38 / 2.23; C3 flat within 0.1 ms from 128)
-      static const int planes_min_np =
-          getenv("SBAG_PLANES_MIN_PARENTS") ? atoi(getenv("SBAG_PLANES_MIN_PARENTS")) : 256;
+      constexpr int planes_min_np = 256;
       const bool lvl_planes = d_planes != nullptr && NP >= planes_min_np;
       auto colkey = [&](int q) {
         if (lvl_planes) return (int64_t)par[q].pos * plane_nsp + par[q].s;
@@ -4627,10 +4552,9 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
     std::vector<std::pair<int64_t, int64_t>> ntseg;  // next slots' tile sub-segments
     // gini bags whose every draw count is 1 (without replacement): a child's class counts are
     // its entries per class, so the next histogram's class-tile grouping sizes are known
-    // (SBAG_TILE_KNOWN=0: counted on the device as before)
-    static const bool known_env = !(getenv("SBAG_TILE_KNOWN") && atoi(getenv("SBAG_TILE_KNOWN")) == 0);
+    // (bags with draw counts above 1 are counted on the device)
     const int kct = g.CT > 0 ? g.CT : NS, kntc = (NS + kct - 1) / kct;
-    const bool known_ok = gini && g.grouped && !tile_res && cmax <= 1 && known_env;
+    const bool known_ok = gini && g.grouped && !tile_res && cmax <= 1;
     std::vector<int64_t> hknown;
     for (int q = 0; q < NPn; q++) {
       const Split& sp = psplit[q];
@@ -4799,7 +4723,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
     known_tiles = nullptr;
     pre_hist = nullptr;
     derive.clear();
-    if (!triples.empty() && gini && fused_sub) {
+    if (!triples.empty() && gini) {
       // the next level's split search derives them (SplitArgs.derive)
       derive.assign((size_t)2 * Mn, -1);
       for (size_t k = 0; k + 2 < triples.size() + 1; k += 3) {
@@ -4811,7 +4735,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
       TRY(ws_typed(c, "triples", triples.size(), &d_tri));
       TRY(h2d(c, d_tri, triples.data(), triples.size()));
       int h = tm.begin(T_SUB);
-      launch_subtract(c->stream, hist_nxt, hist_cur, d_tri, (int)triples.size() / 3, slot_words, gini);
+      launch_subtract(c->stream, hist_nxt, hist_cur, d_tri, (int)triples.size() / 3, slot_words);
       HIP_TRY(hipGetLastError());
       tm.end(h);
     }

@@ -80,13 +80,10 @@ struct HistArgs {
   int32_t rl;            // k_hist_rl (identity byte layout): 1 = 64-bit row addresses, 2 = 32-bit
   int32_t grouped;       // gini: entries grouped by class tile, ParentInfo.tile per segment;
                          // blockIdx.y walks feature tiles only
-  int32_t dw;            // k_hist gather width: 1 (byte loads) or 4 (aligned words + extract)
   int32_t hct;           // gini layout class tile: hist[slot][NS / hct][Fmax][NB][hct]
   int32_t rlpd;          // k_hist_rl: rows loaded this many passes ahead (2 or 3)
   int32_t small;         // k_hist: short segments (deep levels): 256-thread workgroups with
                          // 32-entry gather groups (k_hist<.., 256, 32>)
-  int32_t ablate;        // diagnostics only (SBAG_HIST_ABLATE, wrong results): 1 skips the
-                         // flushes, 2 the LDS zeroing, 4 the row gathers, 8 the LDS atomics
   int32_t pad3_;
 };
 
@@ -299,7 +296,7 @@ void launch_zero_word(hipStream_t st, uint64_t* hist, const int32_t* d_slots, in
 void launch_zero_slots(hipStream_t st, void* hist, const int32_t* d_slots, int nslots,
                        int64_t u32_words_per_slot);
 void launch_subtract(hipStream_t st, void* dst_hist, const void* parent_hist, const int32_t* d_triples,
-                     int ntriples, int64_t words_per_slot, bool u32words);
+                     int ntriples, int64_t words_per_slot);
 void launch_synth(hipStream_t st, uint8_t* codes, int32_t S, int64_t N, int32_t F, uint64_t seed,
                   int32_t num_classes, int32_t* labk);
 void launch_predict(hipStream_t st, const double* X, const void* codes, int code_bytes,

@@ -602,12 +602,10 @@ void launch_split_sample(hipStream_t st, const uint8_t* counts, int64_t N, int64
                          uint32_t* d_rows, int64_t cap, uint32_t* d_nrows, bool gap_sampling) {
   if (nrep == 0 || P == 0) return;
   // few partitions and GapSampling (every fraction <= 0.4): a wave per (replica, partition);
-  // else k_split_sample's lanes walk the partitions (SBAG_SPLIT_SAMPLE_LANES=1 forces them)
-  static const bool lanes_env = getenv("SBAG_SPLIT_SAMPLE_LANES") && atoi(getenv("SBAG_SPLIT_SAMPLE_LANES"));
-  if (P < 64 && gap_sampling && !lanes_env) {
-    // waves per (replica, partition): enough for ~32 waves per replica (SBAG_GAP_WAVES)
-    const int W = getenv("SBAG_GAP_WAVES") ? std::max(1, atoi(getenv("SBAG_GAP_WAVES")))
-                                           : std::max(1, std::min(32, 64 / P));
+  // else k_split_sample's lanes walk the partitions
+  if (P < 64 && gap_sampling) {
+    // waves per (replica, partition): enough for ~32 waves per replica
+    const int W = std::min(32, 64 / P);
     hipLaunchKernelGGL(k_split_sample_gap, dim3((unsigned)(P * W), (unsigned)nrep), dim3(64), 0, st, counts,
                        N, d_part_off, P, d_reps, d_part_state, d_frac, d_rows, cap, d_nrows, R * N, W);
     return;
@@ -928,7 +926,6 @@ __device__ __forceinline__ int wave_incl_scan(int v, int lane) {
   return v;
 }
 
-template <bool STG>
 __global__ __launch_bounds__(256) void k_compact(const uint8_t* __restrict__ counts, int64_t N,
                                                  const int32_t* __restrict__ labk,
                                                  uint64_t* __restrict__ ent, int64_t cap,
@@ -972,7 +969,7 @@ __global__ __launch_bounds__(256) void k_compact(const uint8_t* __restrict__ cou
   // (no barriers between them), their wave totals through LDS, one atomic, then the stores in
   // row order (8 reservations, each a round trip between two barriers, paced the kernel)
   __shared__ int s_it[8][4];
-  __shared__ uint64_t s_stage[STG ? 4 : 1][STG ? 256 : 1];
+  __shared__ uint64_t s_stage[4][256];
   int incl[8], nn[8];
 #pragma unroll
   for (int it = 0; it < 8; it++) {
@@ -1009,40 +1006,27 @@ __global__ __launch_bounds__(256) void k_compact(const uint8_t* __restrict__ cou
       before += w < wave ? s_it[it][w] : 0;
       total += s_it[it][w];
     }
-    if (STG) {
-      // the wave's entries (contiguous in the output) go through its LDS run first, then out
-      // as lane-consecutive 8-byte stores: one 512-byte line run per store instead of 64
-      // lanes' entries scattered over the wave's ~1.3 KB (4 predicated stores per iteration)
-      uint64_t* sw = s_stage[wave];
-      int lp = incl[it] - nn[it];
+    // the wave's entries (contiguous in the output) go through its LDS run first, then out
+    // as lane-consecutive 8-byte stores: one 512-byte line run per store instead of 64
+    // lanes' entries scattered over the wave's ~1.3 KB (4 predicated stores per iteration)
+    uint64_t* sw = s_stage[wave];
+    int lp = incl[it] - nn[it];
 #pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const uint32_t c = (cw[it] >> (8 * j)) & 0xffu;
-        if (c) {
-          const int32_t k = kk[j];
-          mysq += (unsigned long long)c * (unsigned long long)((int64_t)k * k);
-          sw[lp++] = pack_entry((uint32_t)(row0 + j), k, c);
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      const int wn = s_it[it][wave];
-      uint64_t* dst = er + itbase + (unsigned long long)before;
-      for (int q = lane; q < wn; q += 64) dst[q] = sw[q];
-      __builtin_amdgcn_wave_barrier();  // (the run is rewritten by the next iteration)
-    } else {
-      unsigned long long pos = itbase + (unsigned long long)(before + incl[it] - nn[it]);
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const uint32_t c = (cw[it] >> (8 * j)) & 0xffu;
-        if (c) {
-          const int32_t k = kk[j];
-          mysq += (unsigned long long)c * (unsigned long long)((int64_t)k * k);
-          er[pos++] = pack_entry((uint32_t)(row0 + j), k, c);
-        }
+    for (int j = 0; j < 4; j++) {
+      const uint32_t c = (cw[it] >> (8 * j)) & 0xffu;
+      if (c) {
+        const int32_t k = kk[j];
+        mysq += (unsigned long long)c * (unsigned long long)((int64_t)k * k);
+        sw[lp++] = pack_entry((uint32_t)(row0 + j), k, c);
       }
     }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const int wn = s_it[it][wave];
+    uint64_t* dst = er + itbase + (unsigned long long)before;
+    for (int q = lane; q < wn; q += 64) dst[q] = sw[q];
+    __builtin_amdgcn_wave_barrier();  // (the run is rewritten by the next iteration)
     itbase += (unsigned long long)total;
   }
   __shared__ unsigned long long s_sq[4];
@@ -1071,13 +1055,8 @@ void launch_compact(hipStream_t st, const uint8_t* counts, int64_t N, int R, con
                     uint64_t* ent, int64_t cap, unsigned long long* d_cursor,
                     unsigned long long* d_wsum, unsigned int* d_cmax, unsigned long long* d_sqsum) {
   const int64_t chunks = (N + 8191) / 8192;
-  static const bool stg = !getenv("SBAG_COMPACT_STG") || atoi(getenv("SBAG_COMPACT_STG")) != 0;  // (A/B)
-  if (stg)
-    hipLaunchKernelGGL(k_compact<true>, dim3((unsigned)(chunks * R)), dim3(256), 0, st, counts, N, d_labk,
-                       ent, cap, d_cursor, d_wsum, d_cmax, d_sqsum, R);
-  else
-    hipLaunchKernelGGL(k_compact<false>, dim3((unsigned)(chunks * R)), dim3(256), 0, st, counts, N, d_labk,
-                       ent, cap, d_cursor, d_wsum, d_cmax, d_sqsum, R);
+  hipLaunchKernelGGL(k_compact, dim3((unsigned)(chunks * R)), dim3(256), 0, st, counts, N, d_labk, ent, cap,
+                     d_cursor, d_wsum, d_cmax, d_sqsum, R);
 }
 
 // ======================================================================
@@ -1093,8 +1072,7 @@ void launch_compact(hipStream_t st, const uint8_t* counts, int64_t N, int R, con
 // and computes its stat words, then for every entry of the batch the wave
 // broadcasts row and words (readlane), lane fl loads the aligned 4-byte word holding
 // byte pos[fl] of that row straight from the row's cache line (SGPR row base + VGPR
-// column; HistArgs.dw = 1: the byte itself) one group of entries ahead, extracts the
-// byte, and adds the words into
+// column) one group of entries ahead, extracts the byte, and adds the words into
 // [plane][bin][feature] with one LDS atomic per plane.  The LDS atomic pipe is
 // the only shared resource, and it only carries the atomics.
 //
@@ -1115,7 +1093,7 @@ constexpr int kHistWaves = kHistThreads / 64;
 // one is added, so a wave keeps up to 2 groups of row gathers in flight (k_hist is bound
 // by their latency when the atomics are few: 16 for up to two 64-feature lane groups)
 // (gini with one lane group: 8, so that the kernel fits 64 VGPRs at 8 waves per SIMD)
-template <int MODE, int NJ, int GW>
+template <int MODE, int NJ>
 constexpr int hist_group() {
   return (MODE == kHistGini && NJ == 1) || NJ > 2 ? 8 : 16;
 }
@@ -1220,11 +1198,11 @@ __device__ __forceinline__ uint32_t rdlane(uint32_t v, int l) {
   return (uint32_t)__builtin_amdgcn_readlane((int)v, l);
 }
 
-// bytes of the NJ feature columns of entries [u0, u0 + KG) of the batch.  DW: each lane
-// loads the aligned dword holding its byte (posr is then pos & ~3; the add extracts the
+// bytes of the NJ feature columns of entries [u0, u0 + KG) of the batch.  Each lane
+// loads the aligned dword holding its byte (posr is pos & ~3; the add extracts the
 // byte): a wave's 64 lanes touch ~1/4 as many distinct addresses as with byte loads, which
 // for a subspace's scattered columns is what the vector memory path is paced by
-template <int NJ, int KG, int GW>
+template <int NJ, int KG>
 __device__ __forceinline__ void hist_load_group(const uint8_t* __restrict__ binsr, uint32_t S,
                                                 uint32_t row, int u0, const uint32_t (&posr)[NJ],
                                                 uint32_t (&buf)[KG][NJ]) {
@@ -1237,12 +1215,7 @@ __device__ __forceinline__ void hist_load_group(const uint8_t* __restrict__ bins
     const __amdgpu_buffer_rsrc_t rs =
         __builtin_amdgcn_make_buffer_rsrc((void*)rp, (short)0, (int)S, 0x00020000);
 #pragma unroll
-    for (int jj = 0; jj < NJ; jj++) {
-      if (GW == 4)
-        buf[t][jj] = __builtin_amdgcn_raw_buffer_load_b32(rs, posr[jj], 0, 0);
-      else
-        buf[t][jj] = __builtin_amdgcn_raw_buffer_load_b8(rs, posr[jj], 0, 0);
-    }
+    for (int jj = 0; jj < NJ; jj++) buf[t][jj] = __builtin_amdgcn_raw_buffer_load_b32(rs, posr[jj], 0, 0);
   }
 }
 
@@ -1250,14 +1223,14 @@ __device__ __forceinline__ void hist_load_group(const uint8_t* __restrict__ bins
 // (offset wh); the u64 modes add (wh:wl)
 // ONES (gini): every count of the batch is 1 (Bernoulli bags, C5): the added value is the
 // constant 1 and the count readlane and its VGPR copy go away (5 VALU per entry, not 7)
-template <int MODE, int NJ, int KG, int GW, bool ONES = false>
+template <int MODE, int NJ, int KG, bool ONES = false>
 __device__ __forceinline__ void hist_add_group(unsigned char* smem, int u0,
                                                const uint32_t (&buf)[KG][NJ], uint32_t wl,
                                                uint32_t wh, const uint32_t (&amul)[NJ],
                                                const uint32_t (&abase)[NJ],
                                                const uint32_t (&bsh)[NJ]) {
   auto bin = [&](int t, int jj) -> uint32_t {
-    return GW == 4 ? __builtin_amdgcn_ubfe(buf[t][jj], bsh[jj], 8) : buf[t][jj];
+    return __builtin_amdgcn_ubfe(buf[t][jj], bsh[jj], 8);
   };
 #pragma unroll
   for (int t = 0; t < KG; t++) {
@@ -1295,7 +1268,7 @@ __device__ __forceinline__ void hist_add_group(unsigned char* smem, int u0,
 // class tile) sub-segment is a few hundred entries: each wave then holds one or two
 // batches, the barriers around every sub-segment's flush expose the whole chain of gather
 // groups, and 32-entry groups (4 waves per SIMD, 128 VGPRs) cut that chain by 4.
-template <int MODE, int NJ, int GW, int NT = kHistThreads, int KG = hist_group<MODE, NJ, GW>()>
+template <int MODE, int NJ, int NT = kHistThreads, int KG = hist_group<MODE, NJ>()>
 __global__ __launch_bounds__(NT, NT == kHistThreads ? (MODE == kHistGini && NJ == 1 ? 8 : 4) : 4) void k_hist(HistArgs A) {
   constexpr int kWaves = NT / 64;
   extern __shared__ __align__(16) unsigned char smem[];
@@ -1358,11 +1331,10 @@ __global__ __launch_bounds__(NT, NT == kHistThreads ? (MODE == kHistGini && NJ =
     if (slot != cur_slot || tile != cur_tile || acc + (b - a) > A.flush_limit) {
       if (cur_slot >= 0) {
         block_sync();
-        if (!(A.ablate & 1)) hist_flush<MODE>(A, smem, plane, cur_slot, ft0, cur_ftn, c0, nct, cur_store);
+        hist_flush<MODE>(A, smem, plane, cur_slot, ft0, cur_ftn, c0, nct, cur_store);
         block_sync();
-        if (!(A.ablate & 2))
-          for (uint32_t i = (uint32_t)tid * 16; i < hist_bytes; i += NT * 16)
-            *(uint4*)(smem + i) = make_uint4(0, 0, 0, 0);
+        for (uint32_t i = (uint32_t)tid * 16; i < hist_bytes; i += NT * 16)
+          *(uint4*)(smem + i) = make_uint4(0, 0, 0, 0);
         block_sync();
       }
       // a node split over several flushes by this workgroup adds from the second on
@@ -1383,8 +1355,8 @@ __global__ __launch_bounds__(NT, NT == kHistThreads ? (MODE == kHistGini && NJ =
         const int fl = lane + 64 * j;
         const bool ok = fl < ftn;
         const uint32_t pb = ok ? (uint32_t)A.pos[(int64_t)r * A.Fmax + ft0 + fl] : 0u;
-        posr[j] = pb & ~(uint32_t)(GW - 1);
-        bsh[j] = (pb & (uint32_t)(GW - 1)) * 8u;
+        posr[j] = pb & ~3u;
+        bsh[j] = (pb & 3u) * 8u;
         amul[j] = ok ? (uint32_t)FPH * WB : 0u;
         abase[j] = ok ? (uint32_t)fl * WB : dump;
       }
@@ -1428,23 +1400,20 @@ __global__ __launch_bounds__(NT, NT == kHistThreads ? (MODE == kHistGini && NJ =
         wh = (uint32_t)(w >> 32);
       }
       constexpr int kG = KG;
-      const uint32_t rowa = (A.ablate & 4) ? 0u : row;  // diagnostics: every gather hits row 0
       // the batch's group loop; ONES: a full batch whose counts are all 1 (lanes past a
       // piece have c = 0, so a partial batch takes the general path, which adds 0 for them)
       auto groups = [&](auto ones) {
         constexpr bool O = decltype(ones)::value;
         uint32_t bA[kG][NJ], bB[kG][NJ];
-        hist_load_group<NJ, kG, GW>(binsr, S, rowa, 0, posr, bA);
+        hist_load_group<NJ, kG>(binsr, S, row, 0, posr, bA);
 #pragma unroll
         for (int g = 0; g < 64 / kG; g += 2) {
-          if ((g + 1) * kG < n) hist_load_group<NJ, kG, GW>(binsr, S, rowa, (g + 1) * kG, posr, bB);
-          if (!(A.ablate & 8))
-            hist_add_group<MODE, NJ, kG, GW, O>(smem, g * kG, bA, wl, wh, amul, abase, bsh);
+          if ((g + 1) * kG < n) hist_load_group<NJ, kG>(binsr, S, row, (g + 1) * kG, posr, bB);
+          hist_add_group<MODE, NJ, kG, O>(smem, g * kG, bA, wl, wh, amul, abase, bsh);
           if ((g + 1) * kG >= n) break;
           if (g + 2 < 64 / kG && (g + 2) * kG < n)
-            hist_load_group<NJ, kG, GW>(binsr, S, rowa, (g + 2) * kG, posr, bA);
-          if (!(A.ablate & 8))
-            hist_add_group<MODE, NJ, kG, GW, O>(smem, (g + 1) * kG, bB, wl, wh, amul, abase, bsh);
+            hist_load_group<NJ, kG>(binsr, S, row, (g + 2) * kG, posr, bA);
+          hist_add_group<MODE, NJ, kG, O>(smem, (g + 1) * kG, bB, wl, wh, amul, abase, bsh);
           if ((g + 2) * kG >= n) break;
         }
       };
@@ -1454,7 +1423,7 @@ __global__ __launch_bounds__(NT, NT == kHistThreads ? (MODE == kHistGini && NJ =
         groups(std::false_type{});
     }
   }
-  if (cur_slot >= 0 && !(A.ablate & 1)) {
+  if (cur_slot >= 0) {
     block_sync();
     hist_flush<MODE>(A, smem, plane, cur_slot, ft0, cur_ftn, c0, nct, cur_store);
   }
@@ -1750,19 +1719,14 @@ size_t hist_stage_bytes() { return (size_t)kHistWaves * 64 * 8; }
 template <int MODE, int NJ>
 static void launch_hist_t(hipStream_t st, const HistArgs& a, dim3 grid, size_t lds_bytes) {
   if constexpr (MODE == kHistGini && NJ == 1) {
-    if (a.small && a.dw == 4) {
-      set_max_lds((const void*)k_hist<MODE, NJ, 4, 256, 32>, 160 * 1024);
-      hipLaunchKernelGGL((k_hist<MODE, NJ, 4, 256, 32>), grid, dim3(256), lds_bytes, st, a);
+    if (a.small) {
+      set_max_lds((const void*)k_hist<MODE, NJ, 256, 32>, 160 * 1024);
+      hipLaunchKernelGGL((k_hist<MODE, NJ, 256, 32>), grid, dim3(256), lds_bytes, st, a);
       return;
     }
   }
-  if (a.dw == 4) {
-    set_max_lds((const void*)k_hist<MODE, NJ, 4>, 160 * 1024);
-    hipLaunchKernelGGL((k_hist<MODE, NJ, 4>), grid, dim3(kHistThreads), lds_bytes, st, a);
-  } else {
-    set_max_lds((const void*)k_hist<MODE, NJ, 1>, 160 * 1024);
-    hipLaunchKernelGGL((k_hist<MODE, NJ, 1>), grid, dim3(kHistThreads), lds_bytes, st, a);
-  }
+  set_max_lds((const void*)k_hist<MODE, NJ>, 160 * 1024);
+  hipLaunchKernelGGL((k_hist<MODE, NJ>), grid, dim3(kHistThreads), lds_bytes, st, a);
 }
 
 template <int MODE>
@@ -2856,11 +2820,10 @@ void launch_split(hipStream_t st, const SplitArgs& a, int M, bool gini) {
     const size_t fixed = (size_t)a.NS * 8 + 256 * (8 + 4 + 4) + 64;
     const size_t budget = 40 * 1024 > fixed ? 40 * 1024 - fixed : 0;
     int G = (int)std::max<size_t>(1, std::min<size_t>(budget / per_f, (size_t)(256 / std::max(1, a.NB - 1))));
-    if (const char* e = getenv("SBAG_SPLIT_G")) G = atoi(e);
     G = std::max(1, std::min(G, a.Fmax));
     const size_t lds_g = fixed + (size_t)G * per_f;
     set_max_lds((const void*)k_split_gini, 160 * 1024);
-    if (lds_g <= 160 * 1024 && !getenv("SBAG_SPLIT_GINI_V1")) {
+    if (lds_g <= 160 * 1024) {
       hipLaunchKernelGGL(k_split_gini, dim3(M), dim3(256), lds_g, st, a, G);
       return;
     }
@@ -2870,10 +2833,10 @@ void launch_split(hipStream_t st, const SplitArgs& a, int M, bool gini) {
   }
 }
 
-// sibling = parent - smaller child  (triples: dst slot, parent slot, small slot)
-template <typename W>
-__global__ __launch_bounds__(256) void k_subtract(W* __restrict__ dst_hist,
-                                                  const W* __restrict__ par_hist,
+// sibling = parent - smaller child  (triples: dst slot, parent slot, small slot); variance's
+// u64 words (gini derives its siblings in the split search, k_split_gini)
+__global__ __launch_bounds__(256) void k_subtract(uint64_t* __restrict__ dst_hist,
+                                                  const uint64_t* __restrict__ par_hist,
                                                   const int32_t* __restrict__ triples,
                                                   int64_t words) {
   const int t = blockIdx.y;
@@ -2905,16 +2868,12 @@ void launch_zero_slots(hipStream_t st, void* hist, const int32_t* d_slots, int n
 }
 
 void launch_subtract(hipStream_t st, void* dst_hist, const void* parent_hist, const int32_t* d_triples,
-                     int ntriples, int64_t words_per_slot, bool u32words) {
+                     int ntriples, int64_t words_per_slot) {
   if (ntriples <= 0) return;
   const unsigned gx = (unsigned)std::min<int64_t>((words_per_slot + 255) / 256, 64);
   dim3 grid(gx, (unsigned)ntriples);
-  if (u32words)
-    hipLaunchKernelGGL(k_subtract<uint32_t>, grid, dim3(256), 0, st, (uint32_t*)dst_hist,
-                       (const uint32_t*)parent_hist, d_triples, words_per_slot);
-  else
-    hipLaunchKernelGGL(k_subtract<uint64_t>, grid, dim3(256), 0, st, (uint64_t*)dst_hist,
-                       (const uint64_t*)parent_hist, d_triples, words_per_slot);
+  hipLaunchKernelGGL(k_subtract, grid, dim3(256), 0, st, (uint64_t*)dst_hist, (const uint64_t*)parent_hist,
+                     d_triples, words_per_slot);
 }
 
 
@@ -2936,7 +2895,15 @@ void launch_subtract(hipStream_t st, void* dst_hist, const void* parent_hist, co
 // The LUT form it replaces gathered one byte per (row, feature, replica) from multi-MB tables
 // in L2 (955 ms of a C3-sized continuous fit, profiles/r04bf/); a count of the cuts by VALU
 // compares took 32 compares per bin (380 ms, profiles/r05logs/r05e/).
-template <typename CT, typename KT, int kRows>
+// 64-row blocks (one row per lane: ~50 KB of LDS with four replicas, three workgroups per CU;
+// 128-row blocks were slower on a C3-sized continuous fit, 604 vs 563 ms, profiles/r05logs/r05k/)
+constexpr int kBinRows = 64;
+// chunks of row blocks: about 65536 workgroups over the replica groups (C3-sized continuous fit
+// 1024 / 4096 / 16384 / 65536 / 262144: 617 / 632 / 548 / 548 / 523 ms on one box,
+// profiles/r05logs/r05t/)
+constexpr int64_t kBinWgs = 65536;
+
+template <typename CT, typename KT>
 __global__ __launch_bounds__(256) void k_bin_cuts(const CT* __restrict__ codes, int64_t N, int32_t S_codes,
                                                   const int32_t* __restrict__ sub,
                                                   const int32_t* __restrict__ Fr, int32_t Fmax,
@@ -2946,6 +2913,7 @@ __global__ __launch_bounds__(256) void k_bin_cuts(const CT* __restrict__ codes, 
                                                   uint8_t* __restrict__ cols, int32_t ncol, int64_t npad,
                                                   int64_t cols_rstride, int R, int rb, int64_t rows_per_chunk) {
   extern __shared__ __align__(16) uint8_t smem[];
+  constexpr int kRows = kBinRows;
   constexpr int kRpl = kRows / 64;  // rows per lane
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -3170,59 +3138,35 @@ __global__ __launch_bounds__(256) void k_bin_cuts_rows(const CT* __restrict__ co
   }
 }
 
-template <typename CT, typename KT, int kRows>
-static bool launch_bin_cuts_r(hipStream_t st, const CT* codes, int64_t N, int32_t S_codes, const int32_t* d_sub,
-                              const int32_t* d_Fr, int32_t Fmax, int R, const uint32_t* d_cut, int32_t ncp,
-                              const uint8_t* d_z0, uint8_t* out, int32_t S_out, int64_t out_rstride, uint8_t* cols,
-                              int32_t ncol, int64_t npad, int64_t cols_rstride) {
-  const int pb = ((S_out / 4) & 1) ? S_out : S_out + 4;  // (the kernel's bin row pitch)
-  const size_t tiles = (size_t)kRows * (S_codes * sizeof(CT) + 4) + (size_t)kRows * pb;
-  const size_t per_rep = (size_t)Fmax * ncp * sizeof(KT);
-  // replicas per workgroup (they share the staged codes) within the LDS target.  One by default:
-  // the occupancy it buys outweighs re-reading the codes per replica (C3-sized continuous fit,
-  // 64 keys: 57.7 ms per launch at one, 65.9 at two; profiles/r05logs/r05z6/).  SBAG_BIN_RB /
-  // SBAG_BIN_LDS_KB override
-  static const int rb_env = getenv("SBAG_BIN_RB") ? atoi(getenv("SBAG_BIN_RB")) : 0;
-  static const int lds_kb = getenv("SBAG_BIN_LDS_KB") ? atoi(getenv("SBAG_BIN_LDS_KB")) : 52;
-  int rb = rb_env > 0 ? rb_env : 1;
-  while (rb > 1 && tiles + rb * per_rep > (size_t)lds_kb * 1024) rb--;
-  rb = std::max(1, std::min(rb, R));
-  int lg = 0;
-  while ((1 << lg) < ncp) lg++;
-  const size_t lds = tiles + ((rb * per_rep + 15) & ~(size_t)15) + (d_z0 ? ((size_t)rb * Fmax + 15) & ~(size_t)15 : 0);
-  // (the staged code rows: 16-byte pieces, at most kRows / 16 per thread per block)
-  if (lds > 150 * 1024 || (1 << lg) != ncp || S_out % 4 != 0 || (S_codes * sizeof(CT)) % 16 != 0 ||
-      (size_t)kRows * S_codes * sizeof(CT) > (size_t)kRows / 16 * 16 * 256 || npad % kRows != 0 ||
-      getenv("SBAG_BIN_ROWWISE"))
-    return false;
-  // chunks of row blocks: about 65536 workgroups over the replica groups (SBAG_BIN_WGS; C3-sized
-  // continuous fit 1024 / 4096 / 16384 / 65536 / 262144: 617 / 632 / 548 / 548 / 523 ms on one box,
-  // profiles/r05logs/r05t/)
-  static const int64_t wgs = getenv("SBAG_BIN_WGS") ? atoll(getenv("SBAG_BIN_WGS")) : 65536;
-  const int ngrp = (R + rb - 1) / rb;
-  const int64_t nblk = (N + kRows - 1) / kRows;
-  const int64_t nch = std::max<int64_t>(1, std::min<int64_t>(nblk, (wgs + ngrp - 1) / ngrp));
-  const int64_t rpc = (nblk + nch - 1) / nch * kRows;
-  const dim3 g((unsigned)((N + rpc - 1) / rpc), (unsigned)ngrp);
-  set_max_lds((const void*)k_bin_cuts<CT, KT, kRows>, (int)lds);
-  hipLaunchKernelGGL((k_bin_cuts<CT, KT, kRows>), g, dim3(256), lds, st, codes, N, S_codes, d_sub, d_Fr, Fmax,
-                     d_cut, ncp, lg, d_z0, out, S_out, out_rstride, cols, ncol, npad, cols_rstride, R, rb, rpc);
-  return true;
-}
-
 template <typename CT, typename KT>
 static bool launch_bin_cuts_t(hipStream_t st, const CT* codes, int64_t N, int32_t S_codes, const int32_t* d_sub,
                               const int32_t* d_Fr, int32_t Fmax, int R, const uint32_t* d_cut, int32_t ncp,
                               const uint8_t* d_z0, uint8_t* out, int32_t S_out, int64_t out_rstride, uint8_t* cols,
                               int32_t ncol, int64_t npad, int64_t cols_rstride) {
-  // 64-row blocks (one row per lane: ~50 KB of LDS with four replicas, three workgroups per CU)
-  // unless SBAG_BIN_ROWS=128 (C3-sized continuous fit 563 vs 604 ms, profiles/r05logs/r05k/)
-  static const int rows = getenv("SBAG_BIN_ROWS") ? atoi(getenv("SBAG_BIN_ROWS")) : 64;
-  if (rows == 128)
-    return launch_bin_cuts_r<CT, KT, 128>(st, codes, N, S_codes, d_sub, d_Fr, Fmax, R, d_cut, ncp, d_z0, out, S_out,
-                                          out_rstride, cols, ncol, npad, cols_rstride);
-  return launch_bin_cuts_r<CT, KT, 64>(st, codes, N, S_codes, d_sub, d_Fr, Fmax, R, d_cut, ncp, d_z0, out, S_out,
-                                       out_rstride, cols, ncol, npad, cols_rstride);
+  constexpr int kRows = kBinRows;
+  const int pb = ((S_out / 4) & 1) ? S_out : S_out + 4;  // (the kernel's bin row pitch)
+  const size_t tiles = (size_t)kRows * (S_codes * sizeof(CT) + 4) + (size_t)kRows * pb;
+  const size_t per_rep = (size_t)Fmax * ncp * sizeof(KT);
+  // replicas per workgroup (they share the staged codes).  One: the occupancy it buys outweighs
+  // re-reading the codes per replica (C3-sized continuous fit, 64 keys: 57.7 ms per launch at
+  // one, 65.9 at two; profiles/r05logs/r05z6/)
+  constexpr int rb = 1;
+  int lg = 0;
+  while ((1 << lg) < ncp) lg++;
+  const size_t lds = tiles + ((rb * per_rep + 15) & ~(size_t)15) + (d_z0 ? ((size_t)rb * Fmax + 15) & ~(size_t)15 : 0);
+  // (the staged code rows: 16-byte pieces, at most kRows / 16 per thread per block)
+  if (lds > 150 * 1024 || (1 << lg) != ncp || S_out % 4 != 0 || (S_codes * sizeof(CT)) % 16 != 0 ||
+      (size_t)kRows * S_codes * sizeof(CT) > (size_t)kRows / 16 * 16 * 256 || npad % kRows != 0)
+    return false;
+  const int ngrp = (R + rb - 1) / rb;
+  const int64_t nblk = (N + kRows - 1) / kRows;
+  const int64_t nch = std::max<int64_t>(1, std::min<int64_t>(nblk, (kBinWgs + ngrp - 1) / ngrp));
+  const int64_t rpc = (nblk + nch - 1) / nch * kRows;
+  const dim3 g((unsigned)((N + rpc - 1) / rpc), (unsigned)ngrp);
+  set_max_lds((const void*)k_bin_cuts<CT, KT>, (int)lds);
+  hipLaunchKernelGGL((k_bin_cuts<CT, KT>), g, dim3(256), lds, st, codes, N, S_codes, d_sub, d_Fr, Fmax,
+                     d_cut, ncp, lg, d_z0, out, S_out, out_rstride, cols, ncol, npad, cols_rstride, R, rb, rpc);
+  return true;
 }
 
 template <typename CT>
@@ -3464,9 +3408,8 @@ static bool launch_bin_ranked_t(hipStream_t st, const CT* codes, int32_t S_codes
   const size_t lds = bin_ranked_lds((int)sizeof(CT), S_codes, S_out, Fmax, ncp);
   int lg = 0;
   while ((1 << lg) < ncp) lg++;
-  static const int64_t wgs = getenv("SBAG_BIN_WGS") ? atoll(getenv("SBAG_BIN_WGS")) : 65536;
   const int64_t nblk = (capb + kRows - 1) / kRows;
-  const int64_t nch = std::max<int64_t>(1, std::min<int64_t>(nblk, (wgs + R - 1) / R));
+  const int64_t nch = std::max<int64_t>(1, std::min<int64_t>(nblk, (kBinWgs + R - 1) / R));
   const int64_t rpc = (nblk + nch - 1) / nch * kRows;
   const dim3 g((unsigned)((capb + rpc - 1) / rpc), (unsigned)R);
   const int64_t rowb = (int64_t)S_codes * sizeof(CT);  // code row bytes: 16-byte pieces per thread

@@ -15,12 +15,12 @@ Each case goes through every entry point that applies:
 The planner's limits are restated from its formulas, not as bare numbers:
   * predict_tiled_lds (sbag_kernels.hip:3706-3711): kPredRows * (S * code_bytes + 4)
     + chunk_bytes [+ nclasses * kPredRows * 2 in mode aggregation], rounded up to 16;
-  * plan_tiled (sbag_host.cpp:5045-5048): fixed = that with chunk_bytes = 0, lds_cap =
+  * plan_tiled (sbag_host.cpp, its first lines): fixed = that with chunk_bytes = 0, lds_cap =
     160 KB - 512; refuse if fixed + 4096 > lds_cap; budget = min(64 KB, lds_cap - fixed) & ~15;
-  * plan_tiled (sbag_host.cpp:5067-5083): a tree takes one 8-byte PNode per node and one
+  * plan_tiled (its loop over the trees): a tree takes one 8-byte PNode per node and one
     8-byte leaf value per leaf, so a tree of n internal nodes (n + 1 leaves) takes
     (2n + 1) * 8 + (n + 1) * 8 = (3n + 2) * 8 bytes, and is refused above the budget;
-  * plan_tiled (sbag_host.cpp:5084-5086): a chunk is closed when the next tree would pass
+  * plan_tiled (the same loop): a chunk is closed when the next tree would pass
     the budget.
 So the largest comb the tiled kernel holds has (65536 / 8 - 2) / 3 = 2730 internal nodes,
 not 4095: the 4095- and 4096-node combs the issue names both take the global walk, and the
@@ -38,7 +38,7 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
 
 K_PRED_ROWS = 512                  # sbag_kernels.hip:3703 kPredRows
-LDS_CAP = 160 * 1024 - 512         # sbag_host.cpp:5046 lds_cap
+LDS_CAP = 160 * 1024 - 512         # plan_tiled's lds_cap
 K_LDS_MODE_CLASSES = 320           # sbag_internal.h:210 kLdsModeClasses
 
 
@@ -56,7 +56,7 @@ def tree_bytes(n_internal):
 
 
 def host_stride(F):
-    return (F + 15) // 16 * 16     # sbag_host.cpp:5150 Sq (u16 codes of host rows)
+    return (F + 15) // 16 * 16     # sbag_predict's Sq (u16 codes of host rows)
 
 
 def plan_chunks(sizes, budget):
@@ -177,7 +177,7 @@ def code_width(X):
 
 def with_filler(X, distinct):
     """X with one more column of `distinct` values that no tree reads: it sets the code
-    width of the dataset (sbag_host.cpp:1081: the widest dictionary decides)."""
+    width of the dataset (build_dataset: the widest dictionary decides)."""
     assert X.shape[0] >= distinct
     return np.ascontiguousarray(np.column_stack([X, np.arange(X.shape[0]) % distinct]).astype(np.float64))
 
