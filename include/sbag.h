@@ -201,6 +201,20 @@ int sbag_forest_nodes(const sbag_forest* f, int32_t t, sbag_node* nodes_out,
 int sbag_forest_create(int32_t num_trees, const int32_t* num_nodes, const sbag_node* nodes,
                        const int32_t* subspace_len, const int32_t* subspaces, int32_t impurity,
                        sbag_forest** out);
+/* sbag_forest_create plus the per-node impurity stats (DecisionTreeModel's impurityStats
+   column; for a gini tree the class counts of the node's rows): num_stats[t] values per node
+   of tree t, concatenated [num_nodes[t] x num_stats[t]] in tree order.  Same validation as
+   sbag_forest_create, and SBAG_EINVAL for a negative num_stats or a negative or non-finite
+   stat.  The forest returns the stats from sbag_forest_nodes (num_stats from
+   sbag_forest_tree_info), and for a gini forest its class count is the larger of
+   sbag_forest_create's (largest leaf prediction + 1) and the largest num_stats.            */
+int sbag_forest_create_stats(int32_t num_trees, const int32_t* num_nodes, const sbag_node* nodes,
+                             const int32_t* subspace_len, const int32_t* subspaces, int32_t impurity,
+                             const int32_t* num_stats /* [num_trees] */,
+                             const double* stats /* concatenated [num_nodes[t] x num_stats[t]] */,
+                             sbag_forest** out);
+/* class count of a gini forest (the columns sbag_predict_raw fills); 0 for a variance forest */
+int sbag_forest_num_classes(const sbag_forest* f, int32_t* n);
 int sbag_forest_free(sbag_forest* f);
 
 /* device-side timing of the last fit (HIP events on the context stream) */
@@ -297,6 +311,46 @@ int sbag_predict_oob_permuted(sbag_ctx* ctx, const sbag_forest* f, const sbag_da
                               double* out /* host [num_perm x num_rows] */,
                               double* base_out /* host [num_rows] or NULL */,
                               int32_t* n_oob_out /* host [num_rows] or NULL */);
+/* ---- per-class raw predictions of a gini forest (ProbabilisticClassificationModel's
+ * rawPrediction; neither kind is normalised).  raw_out is host [num_rows x num_classes],
+ * row-major; the aggregated trees of a row are all of the forest's (sbag_predict_raw,
+ * sbag_predict_raw_dataset) or its out-of-bag learners (sbag_predict_oob_raw), taken in
+ * learner order.
+ *   SBAG_RAW_VOTES  hard voting: raw[r][c] = the number, as an fp64 value, of the
+ *                   aggregated trees whose prediction for row r is class c.  A row sums to
+ *                   the tree count, or to n_oob[r].
+ *   SBAG_RAW_LEAF   soft voting, RandomForestClassificationModel.predictRaw restated (the
+ *                   sum of the base DecisionTreeClassificationModels' probability vectors):
+ *                   s[c] = 0.0 for every class; for every aggregated tree t, with
+ *                   st[0 .. ns_t) the class counts of the leaf row r reaches and
+ *                   total = st[0] + st[1] + ... summed left to right: if total != 0,
+ *                   s[c] = s[c] + st[c] / total for c < ns_t (classes c >= ns_t unchanged;
+ *                   ns_t, the tree's num_stats, is max label + 1 of its own subbag and may be
+ *                   below the forest's class count).  One tree at a time, sequential fp64.
+ * Columns c >= the forest's class count (sbag_forest_num_classes) are 0.0.  num_rows == 0
+ * is SBAG_OK.  SBAG_EINVAL (nothing written, the context stays usable): a null argument, an
+ * unknown kind, a forest that is not gini, num_classes below the forest's class count,
+ * SBAG_RAW_LEAF on a forest with a tree that carries no stats (sbag_forest_create drops
+ * them; sbag_fit and sbag_forest_create_stats keep them).
+ * sbag_predict_oob_raw: `ds`, `sampler` and `partition_offsets` are sbag_predict_oob's, with
+ * its validation, sampler regimes, 255 cap, learner batches and error codes; row r
+ * aggregates the learners i with counts[i][r] == 0, n_oob_out is sbag_predict_oob's byte
+ * for byte, and a row with n_oob == 0 is a row of 0.0 (never NaN).
+ * u8 / u16 codes whose trees (nodes + per-leaf payload) and classes fit the LDS go through
+ * one fused pass (host rows are binned against the forest's thresholds first, in row
+ * batches as in sbag_predict); everything else walks global memory, one thread per row:
+ * the same bits.                                                                     */
+#define SBAG_RAW_VOTES 0 /* hard voting: raw[r][c] = number of trees that predict class c     */
+#define SBAG_RAW_LEAF 1  /* soft voting: raw[r][c] = in-order sum of the trees' leaf fractions */
+int sbag_predict_raw(sbag_ctx* ctx, const sbag_forest* f, const double* X, int64_t num_rows,
+                     int32_t num_features, int32_t kind, int32_t num_classes,
+                     double* raw_out /* host [num_rows x num_classes], row-major */);
+int sbag_predict_raw_dataset(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* ds,
+                             int32_t kind, int32_t num_classes, double* raw_out);
+int sbag_predict_oob_raw(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* ds,
+                         const sbag_sampler_params* sampler, const int64_t* partition_offsets,
+                         int32_t num_partitions, int32_t kind, int32_t num_classes,
+                         double* raw_out, int32_t* n_oob_out /* host [num_rows] or NULL */);
 /* ordered aggregation of per-learner predictions on the host:
    votes [num_learners x num_rows] fp64, learner order */
 int sbag_aggregate(sbag_ctx* ctx, const double* votes, int32_t num_learners, int64_t num_rows,

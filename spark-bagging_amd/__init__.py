@@ -12,6 +12,7 @@ from .libsvm import SparseRows, load_libsvm  # noqa: F401
 from .ml import (BaggingClassificationModel, BaggingClassifier, BaggingRegressionModel,  # noqa: F401
                  BaggingRegressor, DecisionTreeClassifier, DecisionTreeModel,
                  DecisionTreeRegressor, Frame, even_partitions, java_string_hash, oob_metrics,
-                 oob_permutation_importance, permutation_source_rows)
+                 oob_log_loss, oob_permutation_importance, permutation_source_rows,
+                 raw_to_probability)
 from .gbm import (GBMClassificationModel, GBMClassifier, GBMRegressionModel,  # noqa: F401
                   GBMRegressor)

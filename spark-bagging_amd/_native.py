@@ -17,6 +17,7 @@ SBAG_OK, SBAG_EINVAL, SBAG_EEMPTY, SBAG_EDEVICE, SBAG_ENOMEM, SBAG_EUNSUPPORTED 
 IMPURITY_VARIANCE, IMPURITY_GINI = 0, 1
 AGG_MEAN, AGG_MODE = 0, 1
 OUT_SUM, OUT_VOTES = 2, 3  # device outputs of sbag_predict_dataset_device
+RAW_VOTES, RAW_LEAF = 0, 1  # kinds of sbag_predict_raw: hard / soft voting
 COL_F64, COL_F32, COL_U8 = 0, 1, 2  # sbag_dataset_create_columns
 
 # every symbol include/sbag.h declares (checked by tests/test_abi.py)
@@ -30,6 +31,8 @@ EXPORTED = [
     "sbag_forest_nodes", "sbag_forest_create", "sbag_forest_free", "sbag_forest_timing",
     "sbag_predict", "sbag_predict_dataset", "sbag_aggregate", "sbag_predict_dataset_device",
     "sbag_aggregate_device", "sbag_predict_oob", "sbag_predict_oob_permuted",
+    "sbag_forest_num_classes", "sbag_forest_create_stats", "sbag_predict_raw",
+    "sbag_predict_raw_dataset", "sbag_predict_oob_raw",
 ]
 
 
@@ -144,6 +147,11 @@ def lib():
             "sbag_forest_nodes": [P, i32, P, P],
             "sbag_forest_create": [i32, P, P, P, P, i32, P],
             "sbag_forest_free": [P],
+            "sbag_forest_num_classes": [P, P],
+            "sbag_forest_create_stats": [i32, P, P, P, P, i32, P, P, P],
+            "sbag_predict_raw": [P, P, P, i64, i32, i32, i32, P],
+            "sbag_predict_raw_dataset": [P, P, P, i32, i32, P],
+            "sbag_predict_oob_raw": [P, P, P, ctypes.POINTER(SamplerParams), P, i32, i32, i32, P, P],
             "sbag_forest_timing": [P, ctypes.POINTER(Timing)],
             "sbag_predict": [P, P, P, i64, i32, i32, P, P],
             "sbag_predict_dataset": [P, P, P, i32, P],
@@ -406,15 +414,34 @@ class NativeForest:
         check(lib().sbag_forest_timing(self._h, ctypes.byref(t)))
         return t.as_dict()
 
+    @property
+    def num_classes(self):
+        """Class count of a gini forest (the columns predict_raw fills); 0 for variance."""
+        n = ctypes.c_int32()
+        check(lib().sbag_forest_num_classes(self._h, ctypes.byref(n)))
+        return n.value
+
     @classmethod
-    def from_trees(cls, trees, subspaces, impurity):
+    def from_trees(cls, trees, subspaces, impurity, stats=None):
+        """A forest from node arrays; with `stats` (one [num_nodes, num_stats] array per
+        tree, the impurityStats column) through sbag_forest_create_stats, which keeps them
+        (RAW_LEAF needs a gini forest's class counts)."""
         nn = np.array([len(n) for n in trees], np.int32)
         nodes = np.ascontiguousarray(np.concatenate(trees).astype(NODE_DTYPE))
         sl = np.array([len(s) for s in subspaces], np.int32)
         subs = np.ascontiguousarray(np.concatenate([np.asarray(s, np.int32) for s in subspaces]))
         h = ctypes.c_void_p()
-        check(lib().sbag_forest_create(len(trees), ptr(nn), ptr(nodes), ptr(sl), ptr(subs),
-                                       impurity, ctypes.byref(h)))
+        if stats is None:
+            check(lib().sbag_forest_create(len(trees), ptr(nn), ptr(nodes), ptr(sl), ptr(subs),
+                                           impurity, ctypes.byref(h)))
+            return cls(h, impurity)
+        st = [np.asarray(s, np.float64).reshape(len(n), -1) for s, n in zip(stats, trees)]
+        if len(st) != len(trees):
+            raise IllegalArgumentException(SBAG_EINVAL, "one stats array per tree")
+        ns = np.array([s.shape[1] for s in st], np.int32)
+        flat = np.ascontiguousarray(np.concatenate([s.reshape(-1) for s in st] + [np.zeros(1)]))
+        check(lib().sbag_forest_create_stats(len(trees), ptr(nn), ptr(nodes), ptr(sl), ptr(subs),
+                                             impurity, ptr(ns), ptr(flat), ctypes.byref(h)))
         return cls(h, impurity)
 
     def free(self):
@@ -554,6 +581,50 @@ def predict_oob_permuted(ctx, forest, dataset, *, replacement, sample_ratio, see
     check(lib().sbag_predict_oob_permuted(ctx.handle, forest.handle, dataset.handle, ctypes.byref(p), ptr(off),
                                           P, agg, ptr(feats), K, ptr(src), ptr(out), ptr(base), ptr(n_oob)))
     return out, base, n_oob
+
+
+def _raw_width(forest, num_classes):
+    return forest.num_classes if num_classes is None else int(num_classes)
+
+
+def predict_raw(ctx, forest, X, kind, num_classes=None):
+    """Per-class raw predictions of host rows (sbag_predict_raw): fp64 [N, num_classes]
+    (default: the forest's class count); RAW_VOTES counts the trees per class, RAW_LEAF sums
+    their leaf class fractions in learner order."""
+    X = np.ascontiguousarray(X, np.float64)
+    C = _raw_width(forest, num_classes)
+    raw = np.zeros((X.shape[0], max(C, 0)), np.float64)
+    check(lib().sbag_predict_raw(ctx.handle, forest.handle, ptr(X), X.shape[0], X.shape[1], kind, C,
+                                 ptr(raw)))
+    return raw
+
+
+def predict_raw_dataset(ctx, forest, dataset, kind, num_classes=None):
+    """predict_raw over a device dataset (sbag_predict_raw_dataset)."""
+    C = _raw_width(forest, num_classes)
+    raw = np.zeros((dataset.shape[0], max(C, 0)), np.float64)
+    check(lib().sbag_predict_raw_dataset(ctx.handle, forest.handle, dataset.handle, kind, C, ptr(raw)))
+    return raw
+
+
+def predict_oob_raw(ctx, forest, dataset, *, replacement, sample_ratio, seed, learner_begin, learner_end,
+                    partition_offsets=None, kind, num_classes=None):
+    """Out-of-bag raw predictions (sbag_predict_oob_raw), the sampler arguments as
+    predict_oob's: (raw fp64 [N, num_classes] over the learners that left the row out, a row
+    of 0.0 where there is none; n_oob int32 [N], predict_oob's)."""
+    p = SamplerParams(int(replacement), 0, float(sample_ratio), int(seed), learner_begin, learner_end)
+    off = None
+    P = 1
+    if partition_offsets is not None:
+        off = np.ascontiguousarray(partition_offsets, np.int64)
+        P = len(off) - 1
+    n = dataset.shape[0]
+    C = _raw_width(forest, num_classes)
+    raw = np.zeros((n, max(C, 0)), np.float64)
+    n_oob = np.zeros(n, np.int32)
+    check(lib().sbag_predict_oob_raw(ctx.handle, forest.handle, dataset.handle, ctypes.byref(p), ptr(off),
+                                     P, kind, C, ptr(raw), ptr(n_oob)))
+    return raw, n_oob
 
 
 def aggregate(ctx, votes, agg):

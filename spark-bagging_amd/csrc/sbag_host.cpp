@@ -570,6 +570,10 @@ struct sbag_forest {
   struct DevCopy {
     DevNode* nodes = nullptr;
     int64_t* off = nullptr;
+    // SBAG_RAW_LEAF's general path: every leaf's class fractions [leaves x nclasses]
+    // (leaf_fractions) and the first leaf of each tree, built on first use
+    double* frac = nullptr;
+    int64_t* leaf_off = nullptr;
   };
   std::mutex dev_mu;
   std::map<int, DevCopy> dev;
@@ -579,6 +583,8 @@ struct sbag_forest {
       (void)hipSetDevice(kv.first);
       if (kv.second.nodes) (void)hipFree(kv.second.nodes);
       if (kv.second.off) (void)hipFree(kv.second.off);
+      if (kv.second.frac) (void)hipFree(kv.second.frac);
+      if (kv.second.leaf_off) (void)hipFree(kv.second.leaf_off);
     }
   }
 };
@@ -4890,9 +4896,29 @@ int sbag_forest_timing(const sbag_forest* f, sbag_timing* out) {
 // Model load / JNI round trip: the arrays come from disk or another process, so every
 // link, index and class id the predict kernels will follow is checked first (a bad
 // child link would walk out of the tree or loop forever on the device).
+static int forest_create(int32_t T, const int32_t* num_nodes, const sbag_node* nodes,
+                         const int32_t* sub_len, const int32_t* subs, int32_t impurity,
+                         const int32_t* num_stats, const double* stats, sbag_forest** out);
 int sbag_forest_create(int32_t T, const int32_t* num_nodes, const sbag_node* nodes,
                        const int32_t* sub_len, const int32_t* subs, int32_t impurity,
                        sbag_forest** out) {
+  return forest_create(T, num_nodes, nodes, sub_len, subs, impurity, nullptr, nullptr, out);
+}
+int sbag_forest_create_stats(int32_t T, const int32_t* num_nodes, const sbag_node* nodes,
+                             const int32_t* sub_len, const int32_t* subs, int32_t impurity,
+                             const int32_t* num_stats, const double* stats, sbag_forest** out) {
+  if (!num_stats || !stats) return fail(SBAG_EINVAL, "bad arguments");
+  return forest_create(T, num_nodes, nodes, sub_len, subs, impurity, num_stats, stats, out);
+}
+int sbag_forest_num_classes(const sbag_forest* f, int32_t* n) {
+  if (!f || !n) return fail(SBAG_EINVAL, "bad arguments");
+  *n = f->impurity == SBAG_IMPURITY_GINI ? f->nclasses : 0;
+  return SBAG_OK;
+}
+// (num_stats / stats: sbag_forest_create_stats' per-node impurity stats, or both null)
+static int forest_create(int32_t T, const int32_t* num_nodes, const sbag_node* nodes,
+                         const int32_t* sub_len, const int32_t* subs, int32_t impurity,
+                         const int32_t* num_stats, const double* stats, sbag_forest** out) {
   if (T <= 0 || !num_nodes || !nodes || !sub_len || !subs || !out)
     return fail(SBAG_EINVAL, "bad arguments");
   if (impurity != SBAG_IMPURITY_VARIANCE && impurity != SBAG_IMPURITY_GINI)
@@ -4900,12 +4926,24 @@ int sbag_forest_create(int32_t T, const int32_t* num_nodes, const sbag_node* nod
   auto f = std::make_unique<sbag_forest>();
   f->impurity = impurity;
   f->trees.resize(T);
-  int64_t no = 0, so = 0;
+  int64_t no = 0, so = 0, sto = 0;
   int nclasses = 0;
   for (int t = 0; t < T; t++) {
     const std::string bad = "malformed tree " + std::to_string(t) + ": ";
     if (num_nodes[t] <= 0 || sub_len[t] < 0) return fail(SBAG_EINVAL, bad + "empty");
     HTree& h = f->trees[t];
+    if (num_stats) {
+      if (num_stats[t] < 0 || (impurity == SBAG_IMPURITY_GINI && num_stats[t] > 4096))
+        return fail(SBAG_EINVAL, bad + std::to_string(num_stats[t]) + " stats per node");
+      const int64_t cnt = (int64_t)num_nodes[t] * num_stats[t];
+      for (int64_t i = 0; i < cnt; i++)
+        if (!(stats[sto + i] >= 0 && std::isfinite(stats[sto + i])))
+          return fail(SBAG_EINVAL, bad + "a stat is negative or not finite");
+      h.ns = num_stats[t];
+      h.stats.assign(stats + sto, stats + sto + cnt);
+      sto += cnt;
+      if (impurity == SBAG_IMPURITY_GINI) nclasses = std::max(nclasses, (int)num_stats[t]);
+    }
     h.nodes.assign(nodes + no, nodes + no + num_nodes[t]);
     h.sub.assign(subs + so, subs + so + sub_len[t]);
     for (int32_t g : h.sub)
@@ -4955,12 +4993,14 @@ static int upload_forest(sbag_ctx* c, const sbag_forest* fc, const DevNode** d_n
   std::vector<int64_t> off;
   for (const HTree& t : f->trees) {
     off.push_back((int64_t)dn.size());
+    int32_t leaf = 0;
     for (const sbag_node& n : t.nodes) {
       DevNode d{};
       d.left = n.left;
       d.right = n.right;
       d.value = n.left >= 0 ? n.threshold : n.prediction;
       d.gfeat = n.left >= 0 ? t.sub[n.feature] : 0;
+      d.pad = n.left >= 0 ? 0 : leaf++;
       dn.push_back(d);
     }
   }
@@ -5005,6 +5045,16 @@ static int mode_counters(sbag_ctx* c, int agg, int nclasses, int64_t N, uint16_t
 // thresholds compiled to code space by `tc_of(g, thr)` = the largest code whose
 // value is <= thr, trees chunked to the LDS budget.  false: a tree does not fit
 // (very deep trees / very wide rows) -> the global-memory walk.
+// SBAG_RAW_LEAF: the class fractions of leaf k of a tree, dst[c] = st[c] / total with total
+// the left-to-right sum of the leaf's ns class counts; +0.0 for a leaf whose total is 0 and
+// for the classes [ns, C) the tree's subbag never saw (adding +0.0 changes no bit of the sum)
+static void leaf_fractions(const HTree& h, int k, int C, double* dst) {
+  const double* st = h.stats.data() + (size_t)k * h.ns;
+  double total = 0.0;
+  for (int c = 0; c < h.ns; c++) total = total + st[c];
+  for (int c = 0; c < C; c++) dst[c] = (c < h.ns && total != 0) ? st[c] / total : 0.0;
+}
+
 struct TiledPlan {
   std::vector<PNode> pn;
   std::vector<double> lv;
@@ -5014,7 +5064,9 @@ struct TiledPlan {
 
 template <typename TC>
 static bool plan_tiled(const sbag_forest* f, PredictArgs& pa, int F, TC tc_of, TiledPlan& P,
-                       size_t extra_fixed = 0 /* LDS the kernel holds besides predict_tiled_lds */) {
+                       size_t extra_fixed = 0 /* LDS the kernel holds besides predict_tiled_lds */,
+                       int leaf_w = 0 /* > 0: a leaf's payload is its leaf_w class fractions
+                                         (leaf_fractions), its node's index the leaf's ordinal */) {
   const int L = (int)f->trees.size();
   pa.L = L;
   pa.nclasses = std::max(f->nclasses, 1);
@@ -5051,8 +5103,14 @@ static bool plan_tiled(const sbag_forest* f, PredictArgs& pa, int F, TC tc_of, T
         q.a = (uint32_t)pos[n.left];
         q.b = ((uint32_t)g << 17) | (uint32_t)(tc + 1);
       } else {
-        q.a = 0x80000000u | (uint32_t)(P.lv.size() - P.tl[t]);
-        P.lv.push_back(n.prediction);
+        if (leaf_w > 0) {
+          q.a = 0x80000000u | (uint32_t)((P.lv.size() - P.tl[t]) / (size_t)leaf_w);
+          P.lv.resize(P.lv.size() + (size_t)leaf_w);
+          leaf_fractions(h, k, leaf_w, P.lv.data() + P.lv.size() - leaf_w);
+        } else {
+          q.a = 0x80000000u | (uint32_t)(P.lv.size() - P.tl[t]);
+          P.lv.push_back(n.prediction);
+        }
       }
       P.pn.push_back(q);
     }
@@ -5378,6 +5436,291 @@ int sbag_predict_oob(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds,
     if (sp->replacement) TRY(sampler_overflow(c));
   }
   TRY(d2h(c, out, d_out, (size_t)N));
+  if (n_oob_out) TRY(d2h(c, n_oob_out, d_noob, (size_t)N));
+  return SBAG_OK;
+}
+
+}  // extern "C" (host helpers of the raw-prediction entry points)
+
+// ---- per-class raw predictions (sbag_proba.hip).  A call goes through k_proba_tiled when
+// plan_tiled holds the forest beside the accumulators (u8 / u16 codes, every tree's nodes
+// plus leaf payload within the chunk, classes within the LDS), else through k_proba_walk.
+static int check_raw(const sbag_forest* f, int kind, int num_classes) {
+  if (kind != SBAG_RAW_VOTES && kind != SBAG_RAW_LEAF) return fail(SBAG_EINVAL, "unknown raw prediction kind");
+  if (f->impurity != SBAG_IMPURITY_GINI || f->nclasses <= 0 || f->nclasses > 4096)
+    return fail(SBAG_EINVAL, "raw predictions need a gini forest");
+  if (num_classes < f->nclasses)
+    return fail(SBAG_EINVAL, "num_classes " + std::to_string(num_classes) + " is below the forest's " +
+                                 std::to_string(f->nclasses) + " classes");
+  if (kind == SBAG_RAW_LEAF)
+    for (size_t t = 0; t < f->trees.size(); t++) {
+      const HTree& h = f->trees[t];
+      if (h.ns <= 0 || h.stats.size() != h.nodes.size() * (size_t)h.ns)
+        return fail(SBAG_EINVAL, "tree " + std::to_string(t) + " carries no class counts "
+                                 "(sbag_forest_create_stats keeps them)");
+    }
+  return SBAG_OK;
+}
+
+// every leaf's class fractions on this device (the general path of SBAG_RAW_LEAF), built
+// once per device under the forest's lock; upload_forest has made the device's entry
+static int upload_fractions(sbag_ctx* c, const sbag_forest* fc, const double** d_frac,
+                            const int64_t** d_leaf_off) {
+  sbag_forest* f = const_cast<sbag_forest*>(fc);
+  std::lock_guard<std::mutex> lk(f->dev_mu);
+  sbag_forest::DevCopy& cp = f->dev[c->device];
+  if (!cp.frac) {
+    const int C = f->nclasses;
+    std::vector<double> fr;
+    std::vector<int64_t> lo;
+    int64_t leaves = 0;
+    for (const HTree& t : f->trees) {
+      lo.push_back(leaves);
+      for (size_t k = 0; k < t.nodes.size(); k++)
+        if (t.nodes[k].left < 0) {
+          fr.resize(fr.size() + (size_t)C);
+          leaf_fractions(t, (int)k, C, fr.data() + fr.size() - C);
+          leaves++;
+        }
+    }
+    double* df = nullptr;
+    int64_t* dl = nullptr;
+    if (hipMalloc(&df, std::max<size_t>(fr.size(), 1) * 8) != hipSuccess ||
+        hipMalloc(&dl, std::max<size_t>(lo.size(), 1) * 8) != hipSuccess) {
+      (void)hipGetLastError();
+      if (df) (void)hipFree(df);
+      return fail(SBAG_ENOMEM, "device allocation of the forest's leaf fractions failed");
+    }
+    if (hipMemcpy(df, fr.data(), fr.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dl, lo.data(), lo.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(df);
+      (void)hipFree(dl);
+      return fail(SBAG_EDEVICE, "upload of the forest's leaf fractions failed");
+    }
+    cp.frac = df;
+    cp.leaf_off = dl;
+  }
+  *d_frac = cp.frac;
+  *d_leaf_off = cp.leaf_off;
+  return SBAG_OK;
+}
+
+struct RawRun {
+  bool tiled = false;
+  PredictArgs pa{};             // tiled: the uploaded plan (codes / N set per launch)
+  const DevNode* nodes = nullptr;  // general path
+  const int64_t* off = nullptr;
+  const double* frac = nullptr;
+  const int64_t* leaf_off = nullptr;
+};
+
+// the plan of a raw-prediction pass over codes of `code_bytes` at row stride S (tc_of: a
+// threshold in code space, as plan_tiled's), uploaded; may_tile false: the general path
+template <typename TC>
+static int raw_prepare(sbag_ctx* c, const sbag_forest* f, int kind, int code_bytes, int S, int F,
+                       bool may_tile, TC tc_of, RawRun& R) {
+  const int C = f->nclasses;
+  R.pa.code_bytes = code_bytes;
+  R.pa.S = S;
+  R.pa.agg = kAggMean;  // predict_tiled_lds: the row tile and the chunk; the accumulators are extra
+  TiledPlan P;
+  R.tiled = may_tile && plan_tiled(f, R.pa, F, tc_of, P, proba_acc_lds(kind, C), kind == SBAG_RAW_LEAF ? C : 0);
+  if (R.tiled) return upload_plan(c, P, R.pa);
+  TRY(upload_forest(c, f, &R.nodes, &R.off));
+  if (kind == SBAG_RAW_LEAF) TRY(upload_fractions(c, f, &R.frac, &R.leaf_off));
+  return SBAG_OK;
+}
+
+extern "C" {
+
+int sbag_predict_raw(sbag_ctx* c, const sbag_forest* f, const double* X, int64_t N, int32_t F,
+                     int32_t kind, int32_t num_classes, double* raw_out) {
+  if (!c || !f || !X || !raw_out || N < 0 || F <= 0) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(check_raw(f, kind, num_classes));
+  for (const HTree& t : f->trees)
+    for (int32_t g : t.sub)
+      if (g >= F) return fail(SBAG_EINVAL, "feature vector shorter than a subspace index");
+  if (N == 0) return SBAG_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const int L = (int)f->trees.size();
+  // rows are binned on the device against the forest's own thresholds, as in sbag_predict
+  std::vector<std::vector<double>> T(F);
+  for (const HTree& t : f->trees)
+    for (const sbag_node& n : t.nodes)
+      if (n.left >= 0) T[t.sub[n.feature]].push_back(n.threshold);
+  std::vector<int64_t> toff(F + 1, 0);
+  size_t max_thr = 0;
+  for (int g = 0; g < F; g++) {
+    std::sort(T[g].begin(), T[g].end());
+    T[g].erase(std::unique(T[g].begin(), T[g].end()), T[g].end());
+    toff[g + 1] = toff[g] + (int64_t)T[g].size();
+    max_thr = std::max(max_thr, T[g].size());
+  }
+  const int32_t Sq = (F + 15) / 16 * 16;
+  RawRun R;
+  TRY(raw_prepare(c, f, kind, 2, Sq, F, max_thr <= 65535, [&](int g, double thr) {
+    return (int64_t)(std::lower_bound(T[g].begin(), T[g].end(), thr) - T[g].begin());
+  }, R));
+  double* d_raw;
+  TRY(ws_typed(c, "praw", (size_t)N * num_classes, &d_raw));
+  ProbaArgs q{};
+  q.kind = kind;
+  q.C = f->nclasses;
+  q.Cout = num_classes;
+  q.first = 1;
+  q.t0 = 0;
+  q.t1 = L;
+  double* d_X;
+  if (R.tiled) {
+    std::vector<double> tv((size_t)std::max<int64_t>(toff[F], 1));
+    for (int g = 0; g < F; g++) std::copy(T[g].begin(), T[g].end(), tv.begin() + toff[g]);
+    double* d_T;
+    int64_t* d_toff;
+    TRY(ws_typed(c, "pq_thr", tv.size(), &d_T));
+    TRY(ws_typed(c, "pq_off", toff.size(), &d_toff));
+    TRY(h2d(c, d_T, tv.data(), tv.size()));
+    TRY(h2d(c, d_toff, toff.data(), toff.size()));
+    int64_t batch = std::max<int64_t>(1, std::min<int64_t>(N, ((int64_t)2 << 30) / (8 * (int64_t)F)));
+    if (const char* e = getenv("SBAG_PREDICT_BATCH_ROWS")) batch = std::max<int64_t>(1, std::min<int64_t>(batch, atoll(e)));
+    uint16_t* d_codes;
+    TRY(ws_typed(c, "pX", (size_t)batch * F, &d_X));
+    TRY(ws_typed(c, "pq_codes", (size_t)batch * Sq, &d_codes));
+    for (int64_t r0 = 0; r0 < N; r0 += batch) {
+      const int64_t n = std::min(batch, N - r0);
+      HIP_TRY(hipMemcpyAsync(d_X, X + r0 * F, (size_t)n * F * 8, hipMemcpyHostToDevice, c->stream));
+      launch_quantize(c->stream, d_X, n, F, d_T, d_toff, d_codes, Sq);
+      R.pa.codes = d_codes;
+      R.pa.N = n;
+      q.raw = d_raw + r0 * num_classes;
+      launch_proba_tiled(c->stream, R.pa, q);
+      HIP_TRY(hipGetLastError());
+    }
+  } else {
+    TRY(ws_typed(c, "pX", (size_t)N * F, &d_X));
+    TRY(h2d(c, d_X, X, (size_t)N * F));
+    q.raw = d_raw;
+    launch_proba_walk(c->stream, d_X, nullptr, 1, nullptr, nullptr, N, F, F, R.nodes, R.off, R.frac,
+                      R.leaf_off, q);
+    HIP_TRY(hipGetLastError());
+  }
+  TRY(d2h(c, raw_out, d_raw, (size_t)N * num_classes));
+  return SBAG_OK;
+}
+
+// (shared by the dataset and the out-of-bag call) the dataset against the forest and context
+static int check_raw_dataset(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds) {
+  for (const HTree& t : f->trees)
+    for (int32_t g : t.sub)
+      if (g >= ds->F) return fail(SBAG_EINVAL, "dataset has fewer features than the model");
+  if (ds->ctx->device != c->device)
+    return fail(SBAG_EINVAL, "dataset lives on device " + std::to_string(ds->ctx->device) +
+                                 ", the context on device " + std::to_string(c->device));
+  return SBAG_OK;
+}
+
+static int raw_prepare_dataset(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds, int kind,
+                               RawRun& R) {
+  // TreePoint's `value <= threshold` in the dataset's code space (dict sorted ascending)
+  TRY(raw_prepare(c, f, kind, ds->code_bytes, ds->S, ds->F, ds->code_bytes != 4, [&](int g, double thr) {
+    const std::vector<double>& d = ds->dict[g];
+    return (int64_t)(std::upper_bound(d.begin(), d.end(), thr) - d.begin()) - 1;
+  }, R));
+  R.pa.codes = ds->d_codes;
+  R.pa.N = ds->N;
+  return SBAG_OK;
+}
+
+static void raw_launch_dataset(sbag_ctx* c, const sbag_dataset* ds, const RawRun& R, const ProbaArgs& q) {
+  if (R.tiled)
+    launch_proba_tiled(c->stream, R.pa, q);
+  else
+    launch_proba_walk(c->stream, nullptr, ds->d_codes, ds->code_bytes, ds->d_dict, ds->d_dict_off, ds->N,
+                      ds->F, ds->S, R.nodes, R.off, R.frac, R.leaf_off, q);
+}
+
+int sbag_predict_raw_dataset(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds, int32_t kind,
+                             int32_t num_classes, double* raw_out) {
+  if (!c || !f || !ds || !raw_out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(check_raw(f, kind, num_classes));
+  TRY(check_raw_dataset(c, f, ds));
+  if (ds->N == 0) return SBAG_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  RawRun R;
+  TRY(raw_prepare_dataset(c, f, ds, kind, R));
+  double* d_raw;
+  TRY(ws_typed(c, "praw", (size_t)ds->N * num_classes, &d_raw));
+  ProbaArgs q{};
+  q.kind = kind;
+  q.C = f->nclasses;
+  q.Cout = num_classes;
+  q.first = 1;
+  q.t0 = 0;
+  q.t1 = (int)f->trees.size();
+  q.raw = d_raw;
+  raw_launch_dataset(c, ds, R, q);
+  HIP_TRY(hipGetLastError());
+  TRY(d2h(c, raw_out, d_raw, (size_t)ds->N * num_classes));
+  return SBAG_OK;
+}
+
+// The out-of-bag form: sbag_predict_oob's validation, sampler and learner batches (one
+// counts row per learner of a batch on either path; SBAG_OOB_BATCH_LEARNERS forces the batch
+// size, read on every call).  Between batches the rows' state is raw itself and n_oob.
+int sbag_predict_oob_raw(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds,
+                         const sbag_sampler_params* sp, const int64_t* partition_offsets, int32_t P,
+                         int32_t kind, int32_t num_classes, double* raw_out, int32_t* n_oob_out) {
+  if (!c || !f || !ds || !sp || !raw_out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(check_sampler(sp));
+  TRY(check_raw(f, kind, num_classes));
+  const int L = (int)f->trees.size();
+  if (sp->learner_end - sp->learner_begin != L)
+    return fail(SBAG_EINVAL, "the sampler's learner range holds " +
+                                 std::to_string(sp->learner_end - sp->learner_begin) +
+                                 " learners, the forest " + std::to_string(L) + " trees");
+  const int64_t N = ds->N;
+  if (partition_offsets && P >= 1 && partition_offsets[P] != N)
+    return fail(SBAG_EINVAL, "partition_offsets must end at the dataset's row count");
+  std::vector<int64_t> poff;
+  TRY(check_partitions(P, partition_offsets, N, poff));
+  TRY(check_raw_dataset(c, f, ds));
+  if (N == 0) return SBAG_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  RawRun R;
+  TRY(raw_prepare_dataset(c, f, ds, kind, R));
+  int batch = (int)std::max(1.0, std::min((double)L, std::floor(bins_budget(c) / (double)N)));
+  if (const char* e = getenv("SBAG_OOB_BATCH_LEARNERS")) batch = std::max(1, std::min(L, atoi(e)));
+  double* d_raw;
+  int32_t* d_noob;
+  uint8_t* d_counts;
+  TRY(ws_typed(c, "praw", (size_t)N * num_classes, &d_raw));
+  TRY(ws_typed(c, "oob_n", (size_t)N, &d_noob));
+  TRY(ws_typed(c, "counts", (size_t)batch * N, &d_counts));
+  for (int b0 = 0; b0 < L; b0 += batch) {
+    const int b1 = std::min(L, b0 + batch);
+    sbag_sampler_params sb = *sp;
+    sb.learner_begin = sp->learner_begin + b0;
+    sb.learner_end = sp->learner_begin + b1;
+    TRY(run_sampler(c, &sb, poff, N, d_counts, false));
+    ProbaArgs q{};
+    q.kind = kind;
+    q.C = f->nclasses;
+    q.Cout = num_classes;
+    q.first = b0 == 0;
+    q.t0 = b0;
+    q.t1 = b1;
+    q.counts = d_counts;
+    q.raw = d_raw;
+    q.n_oob = d_noob;
+    raw_launch_dataset(c, ds, R, q);
+    HIP_TRY(hipGetLastError());
+    // (the Poisson overflow flag is rewritten by the next batch's sampler: read it now)
+    if (sp->replacement) TRY(sampler_overflow(c));
+  }
+  TRY(d2h(c, raw_out, d_raw, (size_t)N * num_classes));
   if (n_oob_out) TRY(d2h(c, n_oob_out, d_noob, (size_t)N));
   return SBAG_OK;
 }

@@ -165,7 +165,7 @@ struct DevNode {  // packed tree node for predict
   int32_t left;   // -1 for a leaf
   int32_t right;
   int32_t gfeat;  // global feature index (subspace resolved)
-  int32_t pad;
+  int32_t pad;    // leaf: its ordinal among the tree's leaves, pre-order (k_proba_walk)
 };
 
 // Packed tree for the LDS-tiled predict: children adjacent (right = left + 1).
@@ -335,6 +335,37 @@ void launch_predict_oob(hipStream_t st, const PredictArgs& a, const OobArgs& o);
 void launch_aggregate_oob(hipStream_t st, const double* votes, const uint8_t* counts, int K, int64_t N,
                           int agg, int nclasses, double* out, int32_t* n_oob, int32_t* gmax,
                           uint16_t* gcnt, int64_t gcnt_rows, bool first, bool last);
+// ---- per-class raw predictions (sbag_proba.hip): raw[row][c] over the trees [t0, t1) that
+// count for the row (all of them, or with `counts` those whose bag left the row out), in
+// learner order:
+//   kRawVotes  raw[row][c] = number of those trees predicting class c
+//   kRawLeaf   s = s + frac_t(leaf)[c], frac = the reached leaf's class counts / their sum
+// The carried state between learner batches is raw itself (and n_oob): a batch that is not
+// `first` starts from what raw holds.  Columns [C, Cout) are written 0.0.
+constexpr int kRawVotes = 0, kRawLeaf = 1;
+struct ProbaArgs {
+  int32_t kind;           // kRawVotes / kRawLeaf
+  int32_t C, Cout;        // the forest's class count; columns of raw (>= C)
+  int32_t first;          // raw and n_oob start at zero
+  int32_t t0, t1;         // trees [t0, t1) of the forest
+  const uint8_t* counts;  // [t1 - t0][N] bag multiplicities, or null: every tree counts
+  double* raw;            // [N][Cout], row-major
+  int32_t* n_oob;         // [N] trees counted per row, or null
+};
+// LDS of k_proba_tiled past predict_tiled_lds(agg = kAggMean): its accumulators,
+// u16 [C][512] (votes) or fp64 [C][512] (leaf fractions)
+size_t proba_acc_lds(int kind, int C);
+// k_proba_tiled: k_predict_oob's geometry.  kRawVotes: `a` is the plain plan (one value per
+// leaf); kRawLeaf: the plan's leaf values are C fractions per leaf (tree_leaf / chunk
+// bounds in doubles, a leaf node's index its ordinal in the tree)
+void launch_proba_tiled(hipStream_t st, const PredictArgs& a, const ProbaArgs& q);
+// k_proba_walk: one thread per row over DevNodes in global memory (X fp64 rows, or codes +
+// dictionaries as launch_predict); a leaf's DevNode.pad is its ordinal in the tree, its
+// fractions frac[(leaf_off[t] + pad) * C ..] (kRawLeaf)
+void launch_proba_walk(hipStream_t st, const double* X, const void* codes, int code_bytes,
+                       const double* dict, const int64_t* dict_off, int64_t N, int32_t F, int32_t S,
+                       const DevNode* nodes, const int64_t* tree_off, const double* frac,
+                       const int64_t* leaf_off, const ProbaArgs& q);
 // ---- out-of-bag predictions under permuted features (sbag_oobperm.hip): slot k of a
 // feature batch is sbag_predict_oob with feature feat[k] of row r taken from row src[k][r].
 // Between learner batches a slot's state lives in global memory as the baseline's does:

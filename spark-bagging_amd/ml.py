@@ -578,9 +578,22 @@ class _BaggingModel(_BaggingParams):
     def native_forest(self):
         if self._forest is None:
             imp = self.models[0].impurity if self.models else nat.IMPURITY_VARIANCE
+            # a gini model's leaf class counts travel with the forest (soft-voting raw
+            # predictions); models built from node arrays without stats do without them
+            stats = None
+            if imp == nat.IMPURITY_GINI and all(
+                    m.stats is not None and np.ndim(m.stats) == 2 and np.shape(m.stats)[0] == len(m.nodes)
+                    and np.shape(m.stats)[1] > 0 for m in self.models):
+                stats = [m.stats for m in self.models]
             self._forest = nat.NativeForest.from_trees([m.nodes for m in self.models],
-                                                       self.subspaces, imp)
+                                                       self.subspaces, imp, stats=stats)
         return self._forest
+
+    def _not_probabilistic(self, *_a, **_k):
+        raise nat.IllegalArgumentException(
+            nat.SBAG_EINVAL, f"{type(self).__name__} has no class probabilities (a classification model does)")
+
+    predictRaw = predictProbability = oobProbabilities = oobLogLoss = _not_probabilistic
 
     def transform(self, dataset, device=0, per_tree=False):
         """PredictionModel.transform: one prediction per row (HIP kernel)."""
@@ -798,12 +811,118 @@ class BaggingRegressionModel(_BaggingModel):
                      seed=java_string_hash("org.apache.spark.ml.regression.BaggingRegressionModel"))
 
 
+_VOTING = {"soft": nat.RAW_LEAF, "hard": nat.RAW_VOTES}
+
+
+def raw_to_probability(raw):
+    """Class probabilities of raw predictions [N, C] (host arrays, numpy only): raw / row
+    sum, the sum taken left to right over the classes; a zero row (no learner left the row
+    out) gives a row of NaN."""
+    raw = np.asarray(raw, np.float64)
+    if raw.ndim != 2:
+        raise nat.IllegalArgumentException(nat.SBAG_EINVAL, "raw must be [N, C]")
+    s = np.zeros(raw.shape[0], np.float64)
+    for c in range(raw.shape[1]):
+        s = s + raw[:, c]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return raw / s[:, None]
+
+
+def oob_log_loss(proba, n_oob, y):
+    """Out-of-bag log-loss (host arrays, numpy only): {"metric": "logLoss", "value",
+    "coverage", "numRows"}, the mean of -log(p[r, y[r]]) over the rows some learner left out
+    (n_oob > 0), p clipped to [1e-15, 1 - 1e-15] (a label past the columns has p = 0); NaN
+    when no row is covered."""
+    proba = np.asarray(proba, np.float64)
+    y = np.asarray(y, np.float64)
+    n_oob = np.asarray(n_oob)
+    if not (proba.ndim == 2 and y.shape == n_oob.shape == proba.shape[:1]):
+        raise nat.IllegalArgumentException(nat.SBAG_EINVAL, "proba, n_oob and y differ in length")
+    covered = n_oob > 0
+    n = int(len(y))
+    res = {"metric": "logLoss", "value": float("nan"),
+           "coverage": float(covered.sum()) / n if n else 0.0, "numRows": n}
+    if not covered.any():
+        return res
+    k = y[covered].astype(np.int64)
+    ok = (k >= 0) & (k < proba.shape[1])
+    p = np.where(ok, proba[covered][np.arange(len(k)), np.where(ok, k, 0)], 0.0)
+    p = np.clip(p, 1e-15, 1 - 1e-15)
+    res["value"] = float(-np.mean(np.log(p)))
+    return res
+
+
 class BaggingClassificationModel(_BaggingModel):
     _agg = nat.AGG_MODE
     _spark_class = "org.apache.spark.ml.classification.BaggingClassificationModel"
     _estimator_seed_default = java_string_hash("org.apache.spark.ml.classification.BaggingClassifier")
     _defaults = dict(_BaggingParams._defaults,
                      seed=java_string_hash("org.apache.spark.ml.classification.BaggingClassificationModel"))
+
+    @property
+    def numClasses(self):
+        """The class count of the ensemble (columns of predictRaw): the largest of the
+        trees' own class counts and leaf predictions + 1."""
+        return self.native_forest().num_classes
+
+    @staticmethod
+    def _kind(votingStrategy):
+        if votingStrategy not in _VOTING:
+            raise nat.IllegalArgumentException(
+                nat.SBAG_EINVAL, f"votingStrategy given invalid value {votingStrategy} (one of soft, hard)")
+        return _VOTING[votingStrategy]
+
+    def predictRaw(self, dataset, votingStrategy="soft", device=0):
+        """rawPrediction of every row, fp64 [N, numClasses], not normalised (HIP kernel).
+        "hard": the number of trees voting for each class; "soft": the in-order sum of the
+        trees' leaf class fractions (RandomForestClassificationModel.predictRaw).  Inputs as
+        transform's: host rows, a Frame, sparse rows or a DeviceDataset."""
+        kind = self._kind(votingStrategy)
+        forest = self.native_forest()
+        if isinstance(dataset, nat.DeviceDataset):
+            return nat.predict_raw_dataset(dataset.ctx, forest, dataset, kind)
+        ctx = nat.default_context(device)
+        X = dataset.features if isinstance(dataset, Frame) else dataset
+        if is_sparse(X):
+            ds = nat.DeviceDataset.from_csr(X, np.zeros(X.shape[0]), ctx)
+            try:
+                return nat.predict_raw_dataset(ctx, forest, ds, kind)
+            finally:
+                ds.free()
+        X = np.asarray(X, np.float64)
+        if X.ndim == 1:
+            X = X[None, :]
+        return nat.predict_raw(ctx, forest, X, kind)
+
+    def predictProbability(self, dataset, votingStrategy="soft", device=0):
+        """probability of every row: raw_to_probability(predictRaw(...))."""
+        return raw_to_probability(self.predictRaw(dataset, votingStrategy, device))
+
+    def oobProbabilities(self, dataset, votingStrategy="soft", partition_offsets=None):
+        """Out-of-bag class probabilities on the training data: (proba [N, numClasses],
+        n_oob), each row aggregated over the learners whose bag did not draw it; a row of NaN
+        where there is none.  Inputs as oobPredictions'."""
+        kind = self._kind(votingStrategy)
+        (lb, le), ds, part, own = self._oob_dataset(dataset, partition_offsets)
+        try:
+            raw, n_oob = nat.predict_oob_raw(
+                ds.ctx, self.native_forest(), ds, replacement=self.get("replacement"),
+                sample_ratio=self.get("sampleRatio"), seed=self.get("seed"), learner_begin=lb,
+                learner_end=le, partition_offsets=part, kind=kind)
+        finally:
+            if own:
+                ds.free()
+        return raw_to_probability(raw), n_oob
+
+    def oobLogLoss(self, dataset, votingStrategy="soft", partition_offsets=None):
+        """The out-of-bag log-loss of the model on its training data (oob_log_loss of
+        oobProbabilities against the dataset's labels)."""
+        proba, n_oob = self.oobProbabilities(dataset, votingStrategy, partition_offsets)
+        if isinstance(dataset, nat.DeviceDataset):
+            y = dataset.labels()
+        else:
+            y = dataset.label if isinstance(dataset, Frame) else dataset[1]
+        return oob_log_loss(proba, n_oob, y)
 
 
 class BaggingRegressor(_BaggingEstimator):
