@@ -181,6 +181,43 @@ typedef struct {
 int sbag_fit_booster(sbag_ctx* ctx, const sbag_dataset* ds, const double* labels /* host [N] */,
                      const sbag_booster_params* p, sbag_forest** out);
 
+/* ---- Boosting (SAMME / AdaBoost.R2): the boosted bag and the base learner fit on it ----
+ * BoostingParams.extractBoostedBag (ml/boosting/BoostingParams.scala:127-148): row j of
+ * partition i whose prob is != 0.0 gets `new PoissonDistribution(prob)`, reseeded with
+ * seed + i + j, and one sample(); the bag column BoostingClassifier.train
+ * (ml/classification/BoostingClassifier.scala) and BoostingRegressor.train
+ * (ml/regression/BoostingRegressor.scala) draw with prob = proba * numLines each iteration.
+ * With r = partition_offsets[i] + j: counts_out[r] = 0 when mean[r] == 0.0 (nothing is
+ * drawn), else the first nextPoisson(mean[r]) of a Well19937c seeded by
+ * setSeed((long)(seed + i + j)) (64-bit wrapping addition), with the threshold
+ * p = FastMath.exp(-mean[r]) evaluated per row on the device.  partition_offsets as in
+ * sbag_sample.  SBAG_EINVAL: a negative or non-finite mean; SBAG_EUNSUPPORTED: a mean >= 40
+ * (sbag_sample's limit), a draw above 255, 2^32 rows or more.  After a failure nothing has
+ * been written to counts_out and the context stays usable.  num_rows == 0 is SBAG_OK.      */
+int sbag_sample_boosted(sbag_ctx* ctx, const double* mean /* host [num_rows] */, int64_t seed,
+                        const int64_t* partition_offsets, int32_t num_partitions,
+                        int64_t num_rows, uint8_t* counts_out /* host [num_rows] */);
+/* where the rows of the context's last successful sbag_sample_boosted (num_rows > 0) went */
+typedef struct {
+  int64_t rows_zero;     /* mean == 0.0: no draw                                              */
+  int64_t rows_fast;     /* finished within fast_doubles doubles, state kept in registers     */
+  int64_t rows_general;  /* ran on: second pass with the whole generator state in LDS         */
+  int32_t fast_doubles;  /* nextDouble() calls the register path covers                       */
+  int32_t pad_;
+  double fast_ms, general_ms; /* device time of the two kernels                               */
+} sbag_boosted_stats;
+int sbag_sample_boosted_stats(sbag_ctx* ctx, sbag_boosted_stats* out);
+/* One tree on a given bag with the dataset's own labels: the base learner fit of
+ * BoostingClassifier.train (DecisionTreeClassifier, impurity GINI) and BoostingRegressor.train
+ * (DecisionTreeRegressor, impurity VARIANCE) on extractBoostedBag's rows, through
+ * HasBaseLearner.fitBaseLearner (ml/ensemble/ensembleParams.scala:99-117).  sbag_fit_booster
+ * without a label upload: p->counts is the bag column, p->subspace the features, validation
+ * and error codes are sbag_fit_booster's (an all-zero bag is SBAG_EEMPTY) plus sbag_fit's
+ * label checks.  Returns a forest of one tree that carries its impurity stats (a gini tree's
+ * class counts), as sbag_fit's do.                                                        */
+int sbag_fit_bag(sbag_ctx* ctx, const sbag_dataset* ds, const sbag_booster_params* p,
+                 sbag_forest** out);
+
 /* ---- forest (BaggingRegressionModel / BaggingClassificationModel fields
  *      `subspaces`, `models`, `numBaseModels`, BaggingRegressor.scala:235-246) */
 typedef struct { /* DecisionTreeModelReadWrite.NodeData, pre-order ids */

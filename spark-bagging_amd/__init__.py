@@ -16,3 +16,5 @@ from .ml import (BaggingClassificationModel, BaggingClassifier, BaggingRegressio
                  raw_to_probability)
 from .gbm import (GBMClassificationModel, GBMClassifier, GBMRegressionModel,  # noqa: F401
                   GBMRegressor)
+from .boosting import (BoostingClassificationModel, BoostingClassifier,  # noqa: F401
+                       BoostingRegressionModel, BoostingRegressor)

@@ -33,6 +33,7 @@ EXPORTED = [
     "sbag_aggregate_device", "sbag_predict_oob", "sbag_predict_oob_permuted",
     "sbag_forest_num_classes", "sbag_forest_create_stats", "sbag_predict_raw",
     "sbag_predict_raw_dataset", "sbag_predict_oob_raw",
+    "sbag_sample_boosted", "sbag_sample_boosted_stats", "sbag_fit_bag",
 ]
 
 
@@ -97,6 +98,16 @@ class Timing(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class BoostedStats(ctypes.Structure):
+    _fields_ = [("rows_zero", ctypes.c_int64), ("rows_fast", ctypes.c_int64),
+                ("rows_general", ctypes.c_int64), ("fast_doubles", ctypes.c_int32),
+                ("pad_", ctypes.c_int32), ("fast_ms", ctypes.c_double),
+                ("general_ms", ctypes.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad_"}
+
+
 NODE_DTYPE = np.dtype([("id", "<i4"), ("left", "<i4"), ("right", "<i4"), ("feature", "<i4"),
                        ("split_bin", "<i4"), ("pad", "<i4"), ("threshold", "<f8"),
                        ("prediction", "<f8"), ("impurity", "<f8"), ("gain", "<f8")])
@@ -141,6 +152,9 @@ def lib():
             "sbag_dataset_import": [P, i64, i32, i32, i32, P, i32, P, P, P, P],
             "sbag_fit": [P, P, ctypes.POINTER(FitParams), P],
             "sbag_fit_booster": [P, P, P, ctypes.POINTER(BoosterParams), P],
+            "sbag_sample_boosted": [P, P, i64, P, i32, i64, P],
+            "sbag_sample_boosted_stats": [P, ctypes.POINTER(BoostedStats)],
+            "sbag_fit_bag": [P, P, ctypes.POINTER(BoosterParams), P],
             "sbag_forest_num_trees": [P, P],
             "sbag_forest_tree_info": [P, i32, P, P, P, P],
             "sbag_forest_subspace": [P, i32, P],
@@ -523,6 +537,52 @@ def fit_booster(ctx, dataset, labels, counts, subspace, *, partition_offsets=Non
     check(lib().sbag_fit_booster(ctx.handle, dataset.handle, ptr(labels), ctypes.byref(bp),
                                  ctypes.byref(h)))
     return NativeForest(h, IMPURITY_VARIANCE)
+
+
+def sample_boosted(ctx, mean, seed, partition_offsets=None):
+    """The boosted bag (sbag_sample_boosted): row j of partition i draws one
+    Poisson(mean[r]) from a Well19937c seeded with seed + i + j; rows with mean 0.0 get 0."""
+    mean = np.ascontiguousarray(mean, np.float64).reshape(-1)
+    off = None
+    P = 1
+    if partition_offsets is not None:
+        off = np.ascontiguousarray(partition_offsets, np.int64)
+        P = len(off) - 1
+    seed = ((int(seed) + 2**63) % 2**64) - 2**63  # Long arithmetic wraps
+    out = np.zeros(len(mean), np.uint8)
+    check(lib().sbag_sample_boosted(ctx.handle, ptr(mean), seed, ptr(off), P, len(mean), ptr(out)))
+    return out
+
+
+def sample_boosted_stats(ctx):
+    """Rows per path and kernel times of the context's last sample_boosted."""
+    s = BoostedStats()
+    check(lib().sbag_sample_boosted_stats(ctx.handle, ctypes.byref(s)))
+    return s.as_dict()
+
+
+def fit_bag(ctx, dataset, counts, subspace, *, impurity, partition_offsets=None, max_depth=5,
+            max_bins=32, min_instances_per_node=1, min_info_gain=0.0, tree_seed=None):
+    """One tree on the bag `counts` (u8 per row) sliced to `subspace`, with the dataset's own
+    labels (sbag_fit_bag): the Boosting estimators' base-learner fit."""
+    if tree_seed is None:
+        tree_seed = DT_SEED_CLASSIFIER if impurity == IMPURITY_GINI else DT_SEED_REGRESSOR
+    counts = np.ascontiguousarray(counts, np.uint8)
+    sub = np.ascontiguousarray(subspace, np.int32)
+    if len(counts) != dataset.shape[0]:
+        raise IllegalArgumentException(SBAG_EINVAL, "counts do not match the row count")
+    off = None
+    P = 1
+    if partition_offsets is not None:
+        off = np.ascontiguousarray(partition_offsets, np.int64)
+        P = len(off) - 1
+    bp = BoosterParams(counts.ctypes.data, sub.ctypes.data, len(sub), P,
+                       off.ctypes.data if off is not None else None,
+                       TreeParams(max_depth, max_bins, min_instances_per_node, impurity,
+                                  float(min_info_gain), int(tree_seed)))
+    h = ctypes.c_void_p()
+    check(lib().sbag_fit_bag(ctx.handle, dataset.handle, ctypes.byref(bp), ctypes.byref(h)))
+    return NativeForest(h, impurity)
 
 
 def predict(ctx, forest, X, agg, per_tree=False):

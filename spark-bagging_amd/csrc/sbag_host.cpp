@@ -205,6 +205,7 @@ struct sbag_ctx {
   // fits: a fresh buffer per fit page-faulted on every first copy and was unmapped at its end
   std::unique_ptr<int64_t[]> h_sst;
   size_t h_sst_cap = 0;
+  sbag_boosted_stats boost_stats{};  // of the last sbag_sample_boosted that drew a bag
   Reaper reaper;  // (last: destroyed first, after its pending frees)
 };
 #define CTX_LOCK(c) std::lock_guard<std::recursive_mutex> ctx_lock_((c)->mu)
@@ -6018,19 +6019,11 @@ int sbag_aggregate_device(sbag_ctx* c, const void* d_in, int32_t in_bytes, int32
 // engine for dyadic ones.  (Round 3's engine, one lane per (node, feature) walking a node's
 // rows with host split selection, was removed in round 6.)
 
-extern "C" {
-
-int sbag_fit_booster(sbag_ctx* c, const sbag_dataset* ds, const double* labels,
-                     const sbag_booster_params* bp, sbag_forest** out) {
-  if (!c || !ds || !labels || !bp || !out || !bp->counts || !bp->subspace)
-    return fail(SBAG_EINVAL, "bad arguments");
-  if (ds->ctx->device != c->device)
-    return fail(SBAG_EINVAL, "dataset lives on device " + std::to_string(ds->ctx->device) +
-                                 ", the context on device " + std::to_string(c->device));
-  CTX_LOCK(c);
+// the tree params, row count and subspace of a sbag_booster_params (sbag_fit_booster,
+// sbag_fit_bag); sub: the subspace as a vector
+static int check_booster_params(const sbag_dataset* ds, const sbag_booster_params* bp,
+                                std::vector<int32_t>& sub) {
   const sbag_tree_params& tp = bp->tree;
-  if (tp.impurity != SBAG_IMPURITY_VARIANCE)
-    return fail(SBAG_EINVAL, "the booster engine fits DecisionTreeRegressor (impurity variance)");
   if (tp.max_depth < 0 || tp.max_depth > 30)
     return fail(SBAG_EINVAL, "maxDepth given invalid value (must be in [0, 30])");
   if (tp.max_bins < 2 || tp.max_bins > 256)
@@ -6050,10 +6043,160 @@ int sbag_fit_booster(sbag_ctx* c, const sbag_dataset* ds, const double* labels,
   if (Fr <= 0)
     return fail(SBAG_EINVAL, "requirement failed: VectorSlicer requires that at least one "
                              "feature be selected.");
-  std::vector<int32_t> sub(bp->subspace, bp->subspace + Fr);
+  sub.assign(bp->subspace, bp->subspace + Fr);
   for (int k = 0; k < Fr; k++)
     if (sub[k] < 0 || sub[k] >= F || (k > 0 && sub[k] <= sub[k - 1]))
       return fail(SBAG_EINVAL, "subspace indices must be increasing and within [0, num_features)");
+  return SBAG_OK;
+}
+
+// fit_range on a given bag column: the one-learner sampler params FitExt rides on
+static sbag_fit_params ext_fit_params(const sbag_booster_params* bp) {
+  sbag_fit_params fp{};
+  fp.sampler.replacement = 1;
+  fp.sampler.sample_ratio = 1.0;
+  fp.sampler.seed = 0;
+  fp.sampler.learner_begin = 0;
+  fp.sampler.learner_end = 1;
+  fp.subspace_ratio = 1.0;
+  fp.subspace_bug_compat = 0;
+  fp.num_partitions = bp->num_partitions;
+  fp.partition_offsets = bp->partition_offsets;
+  fp.tree = bp->tree;
+  return fp;
+}
+
+extern "C" {
+
+// ====================================================================== boosting
+// BoostingParams.extractBoostedBag (ml/boosting/BoostingParams.scala:127-148) and the base
+// learner fit of BoostingClassifier / BoostingRegressor.train on it.
+
+int sbag_sample_boosted(sbag_ctx* c, const double* mean, int64_t seed, const int64_t* partition_offsets,
+                        int32_t P, int64_t N, uint8_t* counts_out) {
+  if (!c || N < 0 || (N > 0 && (!mean || !counts_out))) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  std::vector<int64_t> poff;
+  TRY(check_partitions(P, partition_offsets, N, poff));
+  if (N >= ((int64_t)1 << 32)) return fail(SBAG_EUNSUPPORTED, "boosted bag of 2^32 rows or more");
+  if (N == 0) return SBAG_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  double *d_mean, *d_tab;
+  int64_t* d_poff;
+  uint8_t* d_counts;
+  uint32_t* d_list;
+  unsigned int* d_flags;
+  TRY(ws_typed(c, "bb_mean", (size_t)N, &d_mean));
+  TRY(ws_typed(c, "bb_tab", (size_t)(84 + 2 * 1025), &d_tab));
+  TRY(ws_typed(c, "poff", poff.size(), &d_poff));
+  TRY(ws_typed(c, "counts", (size_t)N, &d_counts));
+  TRY(ws_typed(c, "bb_list", (size_t)N, &d_list));
+  TRY(ws_typed(c, "bb_flags", 4, &d_flags));
+  TRY(h2d(c, d_mean, mean, (size_t)N));
+  TRY(h2d(c, d_poff, poff.data(), poff.size()));
+  // p = FastMath.exp(-mean) is evaluated per row on the device: sbag_fm_exp_neg's tables
+  TRY(h2d(c, d_tab, sbag_fm_int_a, 42));
+  TRY(h2d(c, d_tab + 42, sbag_fm_int_b, 42));
+  TRY(h2d(c, d_tab + 84, sbag_fm_frac_a, 1025));
+  TRY(h2d(c, d_tab + 84 + 1025, sbag_fm_frac_b, 1025));
+  HIP_TRY(hipMemsetAsync(d_flags, 0, 16, c->stream));
+  hipEvent_t ev[4];
+  for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+  struct EvGuard {
+    hipEvent_t* e;
+    ~EvGuard() {
+      for (int k = 0; k < 4; k++) (void)hipEventDestroy(e[k]);
+    }
+  } guard{ev};
+  const int nparts = (int)poff.size() - 1;
+  HIP_TRY(hipEventRecord(ev[0], c->stream));
+  launch_boost_fast(c->stream, d_mean, N, d_poff, nparts, seed, d_tab, d_counts, d_list, d_flags);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ev[1], c->stream));
+  unsigned int flags[4] = {0, 0, 0, 0};
+  TRY(d2h(c, flags, d_flags, 4));
+  if (flags[0] & 1u)
+    return fail(SBAG_EINVAL, "a boosted bag's mean is negative or not finite");
+  if (flags[0] & 2u)
+    return fail(SBAG_EUNSUPPORTED, "a boosted bag's mean is 40 or more (PoissonDistribution's "
+                                   "large-mean branch is not restated)");
+  const unsigned int nlist = flags[1];
+  if ((int64_t)nlist + (int64_t)flags[2] > N) return fail(SBAG_EDEVICE, "internal: boosted bag row counts");
+  float general_ms = 0.f;
+  if (nlist > 0) {
+    HIP_TRY(hipEventRecord(ev[2], c->stream));
+    launch_boost_ring(c->stream, d_mean, d_poff, nparts, seed, d_tab, d_counts, d_list, nlist, d_flags);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev[3], c->stream));
+    TRY(d2h(c, flags, d_flags, 1));
+    if (flags[0] & 4u) return fail(SBAG_EUNSUPPORTED, "a Poisson draw exceeded 255");
+    HIP_TRY(hipEventElapsedTime(&general_ms, ev[2], ev[3]));
+  }
+  float fast_ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&fast_ms, ev[0], ev[1]));
+  TRY(d2h(c, counts_out, d_counts, (size_t)N));
+  sbag_boosted_stats& s = c->boost_stats;
+  s.rows_zero = (int64_t)flags[2];
+  s.rows_general = (int64_t)nlist;
+  s.rows_fast = N - s.rows_zero - s.rows_general;
+  s.fast_doubles = boost_fast_doubles();
+  s.pad_ = 0;
+  s.fast_ms = fast_ms;
+  s.general_ms = general_ms;
+  return SBAG_OK;
+}
+
+int sbag_sample_boosted_stats(sbag_ctx* c, sbag_boosted_stats* out) {
+  if (!c || !out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  *out = c->boost_stats;
+  return SBAG_OK;
+}
+
+int sbag_fit_bag(sbag_ctx* c, const sbag_dataset* ds, const sbag_booster_params* bp, sbag_forest** out) {
+  if (!c || !ds || !bp || !out || !bp->counts || !bp->subspace) return fail(SBAG_EINVAL, "bad arguments");
+  if (ds->ctx->device != c->device)
+    return fail(SBAG_EINVAL, "dataset lives on device " + std::to_string(ds->ctx->device) +
+                                 ", the context on device " + std::to_string(c->device));
+  CTX_LOCK(c);
+  if (bp->tree.impurity != SBAG_IMPURITY_VARIANCE && bp->tree.impurity != SBAG_IMPURITY_GINI)
+    return fail(SBAG_EINVAL, "unknown impurity");
+  std::vector<int32_t> sub;
+  TRY(check_booster_params(ds, bp, sub));
+  std::vector<int64_t> poff;
+  TRY(check_partitions(bp->num_partitions, bp->partition_offsets, ds->N, poff));
+  {
+    int64_t n_items = 0;
+    for (int64_t r = 0; r < ds->N; r++) n_items += bp->counts[r];
+    if (n_items == 0)
+      return fail(SBAG_EEMPTY, "DecisionTree requires size of input RDD > 0, but was given by "
+                               "empty one.");
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  FitExt ext{bp->counts, sub, &ds->lab};
+  const sbag_fit_params fp = ext_fit_params(bp);
+  sbag_forest* f = nullptr;
+  const int rc = fit_range(c, const_cast<sbag_dataset*>(ds), &fp, &f, &ext);
+  if (rc == kSplitRange) return fail(SBAG_EUNSUPPORTED, "the bag's bins exceed the device budget");
+  TRY(rc);
+  *out = f;
+  return SBAG_OK;
+}
+
+int sbag_fit_booster(sbag_ctx* c, const sbag_dataset* ds, const double* labels,
+                     const sbag_booster_params* bp, sbag_forest** out) {
+  if (!c || !ds || !labels || !bp || !out || !bp->counts || !bp->subspace)
+    return fail(SBAG_EINVAL, "bad arguments");
+  if (ds->ctx->device != c->device)
+    return fail(SBAG_EINVAL, "dataset lives on device " + std::to_string(ds->ctx->device) +
+                                 ", the context on device " + std::to_string(c->device));
+  CTX_LOCK(c);
+  const sbag_tree_params& tp = bp->tree;
+  if (tp.impurity != SBAG_IMPURITY_VARIANCE)
+    return fail(SBAG_EINVAL, "the booster engine fits DecisionTreeRegressor (impurity variance)");
+  std::vector<int32_t> sub;
+  TRY(check_booster_params(ds, bp, sub));
+  const int64_t N = ds->N;
   // host-side phase timing of the booster set-up (SBAG_PROFILE_HOST=1 prints it)
   const bool bprof = getenv("SBAG_PROFILE_HOST") != nullptr;
   auto bnow = [] {
@@ -6118,17 +6261,7 @@ int sbag_fit_booster(sbag_ctx* c, const sbag_dataset* ds, const double* labels,
   HIP_TRY(hipGetLastError());
   bmark(2);  // fixed-point image
   FitExt ext{bp->counts, sub, &lab};
-  sbag_fit_params fp{};
-  fp.sampler.replacement = 1;
-  fp.sampler.sample_ratio = 1.0;
-  fp.sampler.seed = 0;
-  fp.sampler.learner_begin = 0;
-  fp.sampler.learner_end = 1;
-  fp.subspace_ratio = 1.0;
-  fp.subspace_bug_compat = 0;
-  fp.num_partitions = bp->num_partitions;
-  fp.partition_offsets = bp->partition_offsets;
-  fp.tree = tp;
+  const sbag_fit_params fp = ext_fit_params(bp);
   sbag_forest* f = nullptr;
   const int rc = fit_range(c, const_cast<sbag_dataset*>(ds), &fp, &f, &ext);
   if (rc == kSplitRange) return fail(SBAG_EUNSUPPORTED, "the booster's bins exceed the device budget");

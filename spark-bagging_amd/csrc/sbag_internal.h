@@ -212,6 +212,17 @@ void launch_poisson(hipStream_t st, uint8_t* counts, int64_t N, const int64_t* d
 void launch_poisson4(hipStream_t st, uint8_t* counts, int64_t N, const int64_t* d_part_off, int P,
                      int R, int learner0, int64_t seed, double p_exp, int icap, bool cap, int lanes,
                      int* d_err);
+// the boosted bag (sbag_boostbag.hip): one freshly seeded Well19937c and one mean per row.
+// d_tab: sbag_fastmath.h's four tables, concatenated.  d_flags: [0] error bits (1 a negative
+// or non-finite mean, 2 a mean >= 40, 4 a draw above 255), [1] rows left to launch_boost_ring
+// (appended to d_list), [2] rows with mean 0.
+int boost_fast_doubles();  // doubles a row may draw on the register path
+void launch_boost_fast(hipStream_t st, const double* d_mean, int64_t N, const int64_t* d_part_off,
+                       int P, int64_t seed, const double* d_tab, uint8_t* d_counts, uint32_t* d_list,
+                       unsigned int* d_flags);
+void launch_boost_ring(hipStream_t st, const double* d_mean, const int64_t* d_part_off, int P,
+                       int64_t seed, const double* d_tab, uint8_t* d_counts, const uint32_t* d_list,
+                       unsigned int nlist, unsigned int* d_flags);
 void launch_bernoulli(hipStream_t st, uint8_t* counts, int64_t N, const int64_t* d_part_off,
                       const int64_t* d_chunk_pre, int P, int64_t chunks_total, int R,
                       int learner0, int64_t seed, double ratio, const uint64_t* d_jump);
