@@ -34,6 +34,7 @@
 #include "sbag_budget.h"
 #include "sbag_fastmath.h"
 #include "sbag_internal.h"
+#include "sbag_mfma_plan.h"
 
 using namespace sbag;
 
@@ -3418,18 +3419,12 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
     // 127 x 128 keeps a 65536-row int32 sum exact).  The root needs no squares plane
     // (words [.][2]): the screen decides from (count, Σck), and the exact path's Σck² comes
     // from k_compact / k_partition reductions and kHistSq launches
-    int nd1 = 1;
-    while (nd1 < 10 && ((uint64_t)(lkmax - lkmin) >> (7 * nd1)) != 0) nd1++;
-    const int64_t kmid = lkmin + (lkmax - lkmin) / 2;
-    int nds = 1;  // balanced base-256 digits of k - kmid: n of them cover [-128 m, 127 m], m = (256^n - 1) / 255
-    for (; nds < 8; nds++) {
-      const int64_t m = (((int64_t)1 << (8 * nds)) - 1) / 255;
-      if (lkmin - kmid >= -128 * m && lkmax - kmid <= 127 * m) break;
-    }
+    // (the choice: mfma_digit_plan, sbag_mfma_plan.h, swept by tests/c/mfma_plan_check.cpp)
     const int dig_env = getenv("SBAG_MFMA_DIGITS") ? atoi(getenv("SBAG_MFMA_DIGITS")) : 0;  // 7 / 8: force (tests)
-    const bool signed_digits = dig_env == 8 || (dig_env != 7 && nds < nd1);
-    if (signed_digits) nd1 = nds;
-    const int64_t dK0 = signed_digits ? -kmid : K0;  // the digits are of k + dK0
+    const MfmaDigitPlan plan = mfma_digit_plan(lkmin, lkmax, dig_env);
+    const int nd1 = plan.nd1;
+    const bool signed_digits = plan.balanced;
+    const int64_t dK0 = plan.dK0;  // the digits are of k + dK0
     const int nd2 = 0;
     if (nd1 + nd2 > 6) mfma_root = false;
     if (mfma_root) {
@@ -3451,7 +3446,7 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
       ma.ND1 = nd1;
       ma.ND = nd1 + nd2;
       ma.K0 = (int32_t)dK0;
-      ma.dbits = signed_digits ? 8 : 7;
+      ma.dbits = plan.dbits;
       ma.hist = (unsigned long long*)hist_cur;
       if (!launch_hist_mfma(c->stream, ma)) return fail(SBAG_EDEVICE, "internal: MFMA root histogram geometry");
       HIP_TRY(hipGetLastError());

@@ -27,6 +27,7 @@
 #include <cstdint>
 
 #include "sbag_internal.h"
+#include "sbag_mfma_plan.h"
 
 namespace sbag {
 
@@ -254,26 +255,16 @@ bool launch_hist_mfma(hipStream_t st, const MfmaHistArgs& a) {
   return true;
 }
 
-// the digits of k' = k + K0: unsigned 7-bit, plane j = (k' >> 7j) & 127 (k' >= 0), or
-// balanced base 256 (int8 digits d_j in [-128, 127], k' = Σ d_j 256^j: each digit the low
-// byte read as signed, the rest carried up); then those of k^2, plane nd1 + j =
+// the digits of k' = k + K0 (mfma_label_digits, sbag_mfma_plan.h: unsigned 7-bit or balanced
+// base 256); then those of k^2, plane nd1 + j =
 // (k^2 >> 7j) & 127 (j < nd2)
 __global__ __launch_bounds__(256) void k_label_digits(const int32_t* __restrict__ labk, int64_t N,
                                                       int32_t K0, int nd1, int nd2, int balanced,
                                                       uint8_t* __restrict__ digits) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (int64_t)gridDim.x * 256) {
     const int64_t k = labk[i];
-    const uint64_t kp = (uint64_t)(k + K0), k2 = (uint64_t)((int64_t)k * k);
-    if (balanced) {
-      int64_t v = k + K0;
-      for (int j = 0; j < nd1; j++) {
-        const int64_t d = (int64_t)(int8_t)(uint8_t)(v & 0xFF);
-        digits[(int64_t)j * N + i] = (uint8_t)d;
-        v = (v - d) / 256;  // (exact)
-      }
-    } else {
-      for (int j = 0; j < nd1; j++) digits[(int64_t)j * N + i] = (uint8_t)((kp >> (7 * j)) & 127u);
-    }
+    const uint64_t k2 = (uint64_t)((int64_t)k * k);
+    mfma_label_digits(k + K0, nd1, balanced != 0, digits + i, N);
     for (int j = 0; j < nd2; j++) digits[(int64_t)(nd1 + j) * N + i] = (uint8_t)((k2 >> (7 * j)) & 127u);
   }
 }
