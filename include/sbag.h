@@ -388,6 +388,54 @@ int sbag_predict_oob_raw(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset
                          const sbag_sampler_params* sampler, const int64_t* partition_offsets,
                          int32_t num_partitions, int32_t kind, int32_t num_classes,
                          double* raw_out, int32_t* n_oob_out /* host [num_rows] or NULL */);
+/* ---- Stacking: the level-1 dataset and the two-level transform -----------------------------
+ * StackingRegressor.train (ml/regression/StackingRegressor.scala:163-171) and
+ * StackingClassifier.train (ml/classification/StackingClassifier.scala:164-172) map every
+ * training row to Vectors.dense(models.map(_.predict(features))) and fit the stacker on that
+ * DataFrame.  sbag_dataset_create_stacked builds it on the device: `base` holds the K fitted
+ * base learners (one tree each, e.g. K sbag_fit_bag trees joined by sbag_forest_create), and
+ * the result is the dataset sbag_dataset_create would build from the host matrix
+ * P[r][k] = tree_k(row r of ds) and ds's labels, byte for byte what sbag_dataset_export and
+ * sbag_dataset_layout return for it: the same dictionaries (only values some row takes; -0.0
+ * and 0.0 one value; equal predictions of different leaves one value; a leaf no row of ds
+ * reaches contributes nothing), the same code width (u8 up to 256 values in the widest
+ * feature, else u16), the same row_stride with zero padding columns, the same labels
+ * (real-valued ones included; the new dataset owns its label images) and the same 256 bytes
+ * of zero slack behind the codes.  ds need not be the data the trees were fitted on.
+ * Feature k takes at most as many values as tree k has leaves, so its dictionary is the sorted
+ * distinct values of the reached leaves: one pass walks the trees (in LDS chunks, any number
+ * of them) writing leaf ordinals and per-leaf reached flags, the host compacts the per-tree
+ * dictionaries (a few hundred doubles), a second pass maps ordinals to codes.  No array of
+ * num_rows elements crosses to the host and none is sorted there.  A forest whose trees do
+ * not fit an LDS chunk, a ds with u32 codes, and every call under SBAG_STACK_FORCE_FALLBACK,
+ * take the host ingest (sbag_dataset_create's) fed by the per-tree predictions: the same
+ * bytes, slower.
+ * SBAG_EINVAL: a null argument, a subspace of `base` that reaches past ds's features, ds on
+ * another device, a reached leaf that predicts NaN; SBAG_EEMPTY: as sbag_dataset_create.
+ * After a failure nothing is returned and the context stays usable.                        */
+int sbag_dataset_create_stacked(sbag_ctx* ctx, const sbag_dataset* ds, const sbag_forest* base,
+                                sbag_dataset** out);
+/* StackingRegressionModel.predict (StackingRegressor.scala:233-235) and
+ * StackingClassificationModel.predict (StackingClassifier.scala:233-235):
+ *   out[r] = stack.predict(Vectors.dense(models.map(_.predict(features_r))))
+ * `stack` is a forest of exactly one tree whose subspace has length K = the trees of `base`;
+ * its feature j is base tree subspace[j].  Anything else is SBAG_EINVAL, as is a base subspace
+ * past num_features (or ds's features).  num_rows == 0 is SBAG_OK.
+ * The stacker only ever compares a base prediction with a threshold, so a base leaf is packed
+ * as the rank of its value among its tree's sorted distinct leaf values and a stack node as
+ * the largest rank whose value is <= its threshold; the stack tree's leaf values stay fp64.
+ * One fused pass walks the stack tree per row and evaluates base tree k only when a stack node
+ * tests feature k (a repeated test walks the base tree again).  Host rows are binned against
+ * the base forest's thresholds first, in row batches as in sbag_predict.  When the tested
+ * base trees plus the stack tree do not fit the LDS, when the codes are u32, and under
+ * SBAG_STACK_FORCE_FALLBACK=1, the general path runs: the ranks of all K trees into a
+ * temporary [K][num_rows] buffer (chunk by chunk through the LDS, or by a node walk from
+ * global memory: also SBAG_STACK_FORCE_FALLBACK=2), then the stack tree over it.  Same bits. */
+int sbag_predict_stacked(sbag_ctx* ctx, const sbag_forest* base, const sbag_forest* stack,
+                         const double* X, int64_t num_rows, int32_t num_features,
+                         double* out /* [num_rows] */);
+int sbag_predict_stacked_dataset(sbag_ctx* ctx, const sbag_forest* base, const sbag_forest* stack,
+                                 const sbag_dataset* ds, double* out /* [num_rows] */);
 /* ordered aggregation of per-learner predictions on the host:
    votes [num_learners x num_rows] fp64, learner order */
 int sbag_aggregate(sbag_ctx* ctx, const double* votes, int32_t num_learners, int64_t num_rows,

@@ -18,3 +18,5 @@ from .gbm import (GBMClassificationModel, GBMClassifier, GBMRegressionModel,  # 
                   GBMRegressor)
 from .boosting import (BoostingClassificationModel, BoostingClassifier,  # noqa: F401
                        BoostingRegressionModel, BoostingRegressor)
+from .stacking import (StackingClassificationModel, StackingClassifier,  # noqa: F401
+                       StackingRegressionModel, StackingRegressor)

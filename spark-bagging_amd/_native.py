@@ -34,6 +34,7 @@ EXPORTED = [
     "sbag_forest_num_classes", "sbag_forest_create_stats", "sbag_predict_raw",
     "sbag_predict_raw_dataset", "sbag_predict_oob_raw",
     "sbag_sample_boosted", "sbag_sample_boosted_stats", "sbag_fit_bag",
+    "sbag_dataset_create_stacked", "sbag_predict_stacked", "sbag_predict_stacked_dataset",
 ]
 
 
@@ -155,6 +156,9 @@ def lib():
             "sbag_sample_boosted": [P, P, i64, P, i32, i64, P],
             "sbag_sample_boosted_stats": [P, ctypes.POINTER(BoostedStats)],
             "sbag_fit_bag": [P, P, ctypes.POINTER(BoosterParams), P],
+            "sbag_dataset_create_stacked": [P, P, P, P],
+            "sbag_predict_stacked": [P, P, P, P, i64, i32, P],
+            "sbag_predict_stacked_dataset": [P, P, P, P, P],
             "sbag_forest_num_trees": [P, P],
             "sbag_forest_tree_info": [P, i32, P, P, P, P],
             "sbag_forest_subspace": [P, i32, P],
@@ -365,6 +369,15 @@ class DeviceDataset:
                                         1 if codes_on_device else 0, ptr(d), ptr(off), ptr(y),
                                         ctypes.byref(h)))
         return cls(ctx, h)
+
+    def stacked(self, forest, ctx=None):
+        """The level-1 dataset of a stacking fit (sbag_dataset_create_stacked): feature k of
+        row r is tree k of `forest`'s prediction of row r, the labels are this dataset's.
+        Built on the device; equal to from_numpy of the per-tree prediction matrix."""
+        ctx = ctx or self.ctx
+        h = ctypes.c_void_p()
+        check(lib().sbag_dataset_create_stacked(ctx.handle, self._h, forest.handle, ctypes.byref(h)))
+        return DeviceDataset(ctx, h)
 
     def features(self, row_begin=0, row_end=None):
         n, f = self.shape
@@ -685,6 +698,22 @@ def predict_oob_raw(ctx, forest, dataset, *, replacement, sample_ratio, seed, le
     check(lib().sbag_predict_oob_raw(ctx.handle, forest.handle, dataset.handle, ctypes.byref(p), ptr(off),
                                      P, kind, C, ptr(raw), ptr(n_oob)))
     return raw, n_oob
+
+
+def predict_stacked(ctx, base, stack, X_or_dataset):
+    """StackingModel.predict: the one tree of `stack` over the predictions of `base`'s trees
+    (sbag_predict_stacked for host rows, sbag_predict_stacked_dataset for a DeviceDataset)."""
+    if isinstance(X_or_dataset, DeviceDataset):
+        ds = X_or_dataset
+        out = np.zeros(ds.shape[0], np.float64)
+        check(lib().sbag_predict_stacked_dataset(ctx.handle, base.handle, stack.handle, ds.handle,
+                                                 ptr(out)))
+        return out
+    X = np.ascontiguousarray(X_or_dataset, np.float64)
+    out = np.zeros(X.shape[0], np.float64)
+    check(lib().sbag_predict_stacked(ctx.handle, base.handle, stack.handle, ptr(X), X.shape[0],
+                                     X.shape[1], ptr(out)))
+    return out
 
 
 def aggregate(ctx, votes, agg):

@@ -35,6 +35,7 @@
 #include "sbag_fastmath.h"
 #include "sbag_internal.h"
 #include "sbag_mfma_plan.h"
+#include "sbag_stack_plan.h"
 
 using namespace sbag;
 
@@ -6266,6 +6267,411 @@ int sbag_fit_booster(sbag_ctx* c, const sbag_dataset* ds, const double* labels,
     fprintf(stderr, "[sbag] booster host ms: upload+analysis %.2f items %.2f image %.2f fit %.2f\n",
             bt[0], bt[1], bt[2], bt[4]);
   *out = f;
+  return SBAG_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- stacking
+// StackingRegressor / StackingClassifier (ml/regression/StackingRegressor.scala,
+// ml/classification/StackingClassifier.scala): the level-1 DataFrame of the base learners'
+// predictions and the two-level predict, both in code space.  Level-1 feature k takes the
+// values of base tree k's leaves only, so everything the stacker's fit and walk need of it is
+// an index into the tree's sorted distinct leaf values.
+
+// (ranks, cuts and the per-feature dictionaries: sbag_stack_plan.h)
+static std::vector<double> stack_leaf_values(const HTree& h) {
+  std::vector<double> v;
+  for (const sbag_node& n : h.nodes)
+    if (n.left < 0) v.push_back(n.prediction);
+  return stack_sorted_values(v);
+}
+
+// SBAG_STACK_FORCE_FALLBACK (read on every call): 1 the general path of the transform (ranks
+// chunk by chunk, then the stack tree) and the host ingest of the level-1 dataset; 2 the
+// transform's ranks by the node walk from global memory
+static int stack_force() {
+  const char* e = getenv("SBAG_STACK_FORCE_FALLBACK");
+  return e ? atoi(e) : 0;
+}
+
+static int check_stack_pair(const sbag_forest* base, const sbag_forest* stack) {
+  const size_t K = base->trees.size();
+  if (stack->trees.size() != 1)
+    return fail(SBAG_EINVAL, "the stack forest must hold exactly one tree, got " +
+                                 std::to_string(stack->trees.size()));
+  const HTree& st = stack->trees[0];
+  if (st.sub.size() != K)
+    return fail(SBAG_EINVAL, "the stack tree's subspace has length " + std::to_string(st.sub.size()) +
+                                 ", the base forest " + std::to_string(K) + " trees");
+  for (int32_t g : st.sub)
+    if (g < 0 || (size_t)g >= K) return fail(SBAG_EINVAL, "the stack tree's subspace names no base tree");
+  return SBAG_OK;
+}
+
+struct StackRun {
+  int mode = 0;      // 0 k_predict_stacked; 1 k_stack_walk + k_stack_top; 2 k_stack_rank_walk + k_stack_top
+  int K = 0;
+  PredictArgs pa{};  // mode 1: the base forest's plan, its leaves holding ranks
+  StackArgs sa{};    // mode 0
+  const StackTopNode* d_top = nullptr;
+  const double* d_tlv = nullptr;
+  const DevNode* f_nodes = nullptr;  // mode 2
+  const int64_t* f_off = nullptr;
+  const uint32_t* d_rtab = nullptr;
+  const int64_t* d_loff = nullptr;
+};
+
+template <typename TC>
+static int stack_prepare(sbag_ctx* c, const sbag_forest* base, const sbag_forest* stack, int code_bytes,
+                         int S, int F, bool tiled_ok, TC tc_of, StackRun& R) {
+  const int K = (int)base->trees.size();
+  const HTree& st = stack->trees[0];
+  R.K = K;
+  std::vector<std::vector<double>> vals(K);
+  for (int t = 0; t < K; t++) vals[t] = stack_leaf_values(base->trees[t]);
+  const int force = stack_force();
+  PredictArgs pa{};
+  pa.code_bytes = code_bytes;
+  pa.S = S;
+  pa.agg = kAggMean;
+  TiledPlan P;
+  const bool tiled = tiled_ok && force < 2 && plan_tiled(base, pa, F, tc_of, P);
+  if (tiled)  // a leaf's index: its ordinal -> the rank of its value
+    for (int t = 0; t < K; t++) {
+      const int64_t n1 = t + 1 < K ? P.tn[t + 1] : (int64_t)P.pn.size();
+      for (int64_t i = P.tn[t]; i < n1; i++)
+        if (P.pn[i].a & 0x80000000u)
+          P.pn[i].a = 0x80000000u | stack_rank_of(vals[t], P.lv[P.tl[t] + (P.pn[i].a & 0x7fffffffu)]);
+    }
+  // the stack tree, breadth first (children adjacent)
+  std::vector<int> order{0}, pos(st.nodes.size(), -1);
+  pos[0] = 0;
+  for (size_t k = 0; k < order.size(); k++) {
+    const sbag_node& n = st.nodes[order[k]];
+    if (n.left >= 0) {
+      pos[n.left] = (int)order.size();
+      order.push_back(n.left);
+      pos[n.right] = (int)order.size();
+      order.push_back(n.right);
+    }
+  }
+  std::vector<double> tlv;
+  std::vector<StackTopNode> top;
+  for (int k : order) {
+    const sbag_node& n = st.nodes[k];
+    StackTopNode q{};
+    if (n.left >= 0) {
+      q.a = (uint32_t)pos[n.left];
+      q.k = (uint32_t)st.sub[n.feature];
+      q.cut = stack_rank_cut(vals[q.k], n.threshold);
+    } else {
+      q.a = 0x80000000u | (uint32_t)tlv.size();
+      tlv.push_back(n.prediction);
+    }
+    top.push_back(q);
+  }
+  double* d_tlv;
+  TRY(ws_typed(c, "stk_leaves", std::max<size_t>(tlv.size(), 1), &d_tlv));
+  TRY(h2d(c, d_tlv, tlv.data(), tlv.size()));
+  R.d_tlv = d_tlv;
+  if (tiled && force == 0) {
+    // the fused pass: the base trees some stack node tests, then the stack tree, in one array
+    std::vector<int> slot(K, -1);
+    std::vector<int32_t> root;
+    std::vector<PNode> nodes;
+    bool fits = true;
+    for (const StackTopNode& q : top)
+      if (!(q.a & 0x80000000u) && slot[q.k] < 0) {
+        const int t = (int)q.k;
+        slot[t] = (int)root.size();
+        const uint32_t off = (uint32_t)nodes.size();
+        root.push_back((int32_t)off);
+        const int64_t n1 = t + 1 < K ? P.tn[t + 1] : (int64_t)P.pn.size();
+        for (int64_t i = P.tn[t]; i < n1; i++) {
+          PNode p = P.pn[i];
+          if (!(p.a & 0x80000000u)) p.a += off;
+          nodes.push_back(p);
+        }
+      }
+    const uint32_t sroot = (uint32_t)nodes.size();
+    for (const StackTopNode& q : top) {
+      PNode p{};
+      if (q.a & 0x80000000u) {
+        p.a = q.a;
+      } else {
+        if (slot[q.k] >= 32768 || q.cut >= (1u << 17)) fits = false;
+        p.a = sroot + q.a;
+        p.b = ((uint32_t)slot[q.k] << 17) | (q.cut & 0x1ffffu);
+      }
+      nodes.push_back(p);
+    }
+    StackArgs sa{};
+    sa.code_bytes = code_bytes;
+    sa.S = S;
+    sa.nnodes = (int32_t)nodes.size();
+    sa.nleaves = (int32_t)tlv.size();
+    sa.nroot = (int32_t)root.size();
+    sa.sroot = (int32_t)sroot;
+    if (fits && predict_stacked_lds(sa) <= (size_t)160 * 1024 - 512) {
+      PNode* d_nodes;
+      int32_t* d_root;
+      TRY(ws_typed(c, "stk_nodes", nodes.size(), &d_nodes));
+      TRY(ws_typed(c, "stk_root", std::max<size_t>(root.size(), 1), &d_root));
+      TRY(h2d(c, d_nodes, nodes.data(), nodes.size()));
+      TRY(h2d(c, d_root, root.data(), root.size()));
+      sa.nodes = d_nodes;
+      sa.leaves = d_tlv;
+      sa.root = d_root;
+      R.sa = sa;
+      R.mode = 0;
+      return SBAG_OK;
+    }
+  }
+  StackTopNode* d_top;
+  TRY(ws_typed(c, "stk_top", top.size(), &d_top));
+  TRY(h2d(c, d_top, top.data(), top.size()));
+  R.d_top = d_top;
+  if (tiled) {
+    TRY(upload_plan(c, P, pa));
+    R.pa = pa;
+    R.mode = 1;
+    return SBAG_OK;
+  }
+  TRY(upload_forest(c, base, &R.f_nodes, &R.f_off));
+  std::vector<uint32_t> rtab;  // by a leaf's pre-order ordinal in its tree (DevNode.pad)
+  std::vector<int64_t> loff;
+  for (int t = 0; t < K; t++) {
+    loff.push_back((int64_t)rtab.size());
+    for (const sbag_node& n : base->trees[t].nodes)
+      if (n.left < 0) rtab.push_back(stack_rank_of(vals[t], n.prediction));
+  }
+  uint32_t* d_rtab;
+  int64_t* d_loff;
+  TRY(ws_typed(c, "stk_rtab", rtab.size(), &d_rtab));
+  TRY(ws_typed(c, "stk_loff", loff.size(), &d_loff));
+  TRY(h2d(c, d_rtab, rtab.data(), rtab.size()));
+  TRY(h2d(c, d_loff, loff.data(), loff.size()));
+  R.d_rtab = d_rtab;
+  R.d_loff = d_loff;
+  R.mode = 2;
+  return SBAG_OK;
+}
+
+// n rows (codes [n][S], or for the node walk d_X [n][F] / codes + dictionaries) -> d_out [n];
+// d_ranks: the general path's level-1 ranks, n * K elements of 2 (mode 1) or 4 bytes (mode 2)
+static int stack_launch(sbag_ctx* c, const StackRun& R, const void* codes, int code_bytes, int S, int64_t n,
+                        const double* d_X, int F, const double* d_dict, const int64_t* d_dict_off,
+                        void* d_ranks, double* d_out) {
+  if (R.mode == 0) {
+    StackArgs sa = R.sa;
+    sa.codes = codes;
+    sa.N = n;
+    sa.out = d_out;
+    launch_predict_stacked(c->stream, sa);
+  } else if (R.mode == 1) {
+    PredictArgs pa = R.pa;
+    pa.codes = codes;
+    pa.N = n;
+    launch_stack_walk(c->stream, pa, (uint16_t*)d_ranks, nullptr);
+    HIP_TRY(hipGetLastError());
+    launch_stack_top(c->stream, R.d_top, R.d_tlv, d_ranks, 2, n, d_out);
+  } else {
+    launch_stack_rank_walk(c->stream, d_X, codes, code_bytes, d_dict, d_dict_off, n, F, S, R.f_nodes, R.f_off,
+                           R.K, R.d_rtab, R.d_loff, (uint32_t*)d_ranks);
+    HIP_TRY(hipGetLastError());
+    launch_stack_top(c->stream, R.d_top, R.d_tlv, d_ranks, 4, n, d_out);
+  }
+  HIP_TRY(hipGetLastError());
+  return SBAG_OK;
+}
+
+extern "C" {
+
+int sbag_predict_stacked(sbag_ctx* c, const sbag_forest* base, const sbag_forest* stack, const double* X,
+                         int64_t N, int32_t F, double* out) {
+  if (!c || !base || !stack || !X || !out || N < 0 || F <= 0) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(check_stack_pair(base, stack));
+  for (const HTree& t : base->trees)
+    for (int32_t g : t.sub)
+      if (g >= F) return fail(SBAG_EINVAL, "feature vector shorter than a subspace index");
+  if (N == 0) return SBAG_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  // rows are binned against the base forest's own thresholds, as in sbag_predict
+  std::vector<std::vector<double>> T(F);
+  for (const HTree& t : base->trees)
+    for (const sbag_node& n : t.nodes)
+      if (n.left >= 0) T[t.sub[n.feature]].push_back(n.threshold);
+  std::vector<int64_t> toff(F + 1, 0);
+  size_t max_thr = 0;
+  for (int g = 0; g < F; g++) {
+    std::sort(T[g].begin(), T[g].end());
+    T[g].erase(std::unique(T[g].begin(), T[g].end()), T[g].end());
+    toff[g + 1] = toff[g] + (int64_t)T[g].size();
+    max_thr = std::max(max_thr, T[g].size());
+  }
+  const int32_t Sq = (F + 15) / 16 * 16;
+  StackRun R;
+  TRY(stack_prepare(c, base, stack, 2, Sq, F, max_thr <= 65535, [&](int g, double thr) {
+    return (int64_t)(std::lower_bound(T[g].begin(), T[g].end(), thr) - T[g].begin());
+  }, R));
+  double *d_T = nullptr, *d_out, *d_X;
+  int64_t* d_toff = nullptr;
+  uint16_t* d_codes = nullptr;
+  void* d_ranks = nullptr;
+  if (R.mode < 2) {
+    std::vector<double> tv((size_t)std::max<int64_t>(toff[F], 1));
+    for (int g = 0; g < F; g++) std::copy(T[g].begin(), T[g].end(), tv.begin() + toff[g]);
+    TRY(ws_typed(c, "pq_thr", tv.size(), &d_T));
+    TRY(ws_typed(c, "pq_off", toff.size(), &d_toff));
+    TRY(h2d(c, d_T, tv.data(), tv.size()));
+    TRY(h2d(c, d_toff, toff.data(), toff.size()));
+  }
+  int64_t batch = std::max<int64_t>(1, std::min<int64_t>(N, ((int64_t)2 << 30) / (8 * (int64_t)F)));
+  if (const char* e = getenv("SBAG_PREDICT_BATCH_ROWS")) batch = std::max<int64_t>(1, std::min<int64_t>(batch, atoll(e)));
+  TRY(ws_typed(c, "pout", (size_t)N, &d_out));
+  TRY(ws_typed(c, "pX", (size_t)batch * F, &d_X));
+  if (R.mode < 2) TRY(ws_typed(c, "pq_codes", (size_t)batch * Sq, &d_codes));
+  if (R.mode > 0) TRY(ws_get(c, "stk_rank", (size_t)batch * R.K * (R.mode == 1 ? 2 : 4), &d_ranks));
+  for (int64_t r0 = 0; r0 < N; r0 += batch) {
+    const int64_t n = std::min(batch, N - r0);
+    HIP_TRY(hipMemcpyAsync(d_X, X + r0 * F, (size_t)n * F * 8, hipMemcpyHostToDevice, c->stream));
+    if (R.mode < 2) launch_quantize(c->stream, d_X, n, F, d_T, d_toff, d_codes, Sq);
+    TRY(stack_launch(c, R, d_codes, 2, Sq, n, d_X, F, nullptr, nullptr, d_ranks, d_out + r0));
+  }
+  TRY(d2h(c, out, d_out, (size_t)N));
+  return SBAG_OK;
+}
+
+int sbag_predict_stacked_dataset(sbag_ctx* c, const sbag_forest* base, const sbag_forest* stack,
+                                 const sbag_dataset* ds, double* out) {
+  if (!c || !base || !stack || !ds || !out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(check_stack_pair(base, stack));
+  for (const HTree& t : base->trees)
+    for (int32_t g : t.sub)
+      if (g >= ds->F) return fail(SBAG_EINVAL, "dataset has fewer features than the model");
+  if (ds->ctx->device != c->device)
+    return fail(SBAG_EINVAL, "dataset lives on device " + std::to_string(ds->ctx->device) +
+                                 ", the context on device " + std::to_string(c->device));
+  if (ds->N == 0) return SBAG_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  StackRun R;
+  // TreePoint's `value <= threshold` in the dataset's code space (dict sorted ascending)
+  TRY(stack_prepare(c, base, stack, ds->code_bytes, ds->S, ds->F, ds->code_bytes != 4, [&](int g, double thr) {
+    const std::vector<double>& d = ds->dict[g];
+    return (int64_t)(std::upper_bound(d.begin(), d.end(), thr) - d.begin()) - 1;
+  }, R));
+  double* d_out;
+  void* d_ranks = nullptr;
+  TRY(ws_typed(c, "pout", (size_t)ds->N, &d_out));
+  if (R.mode > 0) TRY(ws_get(c, "stk_rank", (size_t)ds->N * R.K * (R.mode == 1 ? 2 : 4), &d_ranks));
+  TRY(stack_launch(c, R, ds->d_codes, ds->code_bytes, ds->S, ds->N, nullptr, ds->F, ds->d_dict, ds->d_dict_off,
+                   d_ranks, d_out));
+  TRY(d2h(c, out, d_out, (size_t)ds->N));
+  return SBAG_OK;
+}
+
+int sbag_dataset_create_stacked(sbag_ctx* c, const sbag_dataset* ds, const sbag_forest* base,
+                                sbag_dataset** out) {
+  if (!c || !ds || !base || !out) return fail(SBAG_EINVAL, "bad arguments");
+  const int K = (int)base->trees.size();
+  const int64_t N = ds->N;
+  if (K <= 0) return fail(SBAG_EINVAL, "bad arguments");
+  if (N == 0) return fail(SBAG_EEMPTY, "ML algorithm was given empty dataset.");
+  for (const HTree& t : base->trees)
+    for (int32_t g : t.sub)
+      if (g >= ds->F) return fail(SBAG_EINVAL, "dataset has fewer features than the model");
+  if (ds->ctx->device != c->device)
+    return fail(SBAG_EINVAL, "dataset lives on device " + std::to_string(ds->ctx->device) +
+                                 ", the context on device " + std::to_string(c->device));
+  CTX_LOCK(c);
+  HIP_TRY(hipSetDevice(c->device));
+  PredictArgs pa{};
+  pa.code_bytes = ds->code_bytes;
+  pa.S = ds->S;
+  pa.N = N;
+  pa.agg = kAggMean;
+  TiledPlan P;
+  const bool tiled = ds->code_bytes != 4 && stack_force() == 0 &&
+                     plan_tiled(base, pa, ds->F, [&](int g, double thr) {
+                       const std::vector<double>& d = ds->dict[g];
+                       return (int64_t)(std::upper_bound(d.begin(), d.end(), thr) - d.begin()) - 1;
+                     }, P);
+  if (!tiled) {
+    // the host ingest fed by the per-tree predictions: the same bytes, slower
+    void* d_pt = nullptr;
+    TRY(predict_dataset_dev(c, base, ds, kAggVotes, 8, nullptr, &d_pt));
+    std::vector<double> pt((size_t)K * N), X((size_t)N * K);
+    TRY(d2h(c, pt.data(), (const double*)d_pt, pt.size()));
+    for (int k = 0; k < K; k++)
+      for (int64_t i = 0; i < N; i++) X[(size_t)i * K + k] = pt[(size_t)k * N + i];
+    DsSource src;
+    src.kind = 0;
+    src.X = X.data();
+    TRY(check_source(src, N, K));
+    return build_dataset(c, N, K, src, ds->lab.y.data(), out);
+  }
+  // pass 1: every row's leaf ordinal per tree, and which leaves are reached
+  const size_t nleaves = P.lv.size();
+  TRY(upload_plan(c, P, pa));
+  pa.codes = ds->d_codes;
+  uint16_t* d_idx;
+  uint32_t* d_present;
+  TRY(ws_typed(c, "stk_rank", (size_t)N * K, &d_idx));
+  TRY(ws_typed(c, "stk_present", nleaves, &d_present));
+  HIP_TRY(hipMemsetAsync(d_present, 0, nleaves * 4, c->stream));
+  launch_stack_walk(c->stream, pa, d_idx, d_present);
+  HIP_TRY(hipGetLastError());
+  std::vector<uint32_t> present(nleaves);
+  TRY(d2h(c, present.data(), d_present, nleaves));
+  // the dictionaries: per tree, a few hundred values
+  auto nd = std::make_unique<sbag_dataset>();
+  nd->ctx = c;
+  nd->N = N;
+  nd->F = K;
+  nd->S = row_stride(K);
+  nd->dict.resize(K);
+  nd->zero_code.assign(K, -1);
+  std::vector<uint16_t> map(nleaves);
+  std::vector<int32_t> moff(K);
+  size_t maxd = 0;
+  for (int t = 0; t < K; t++) {
+    const int64_t l1 = t + 1 < K ? P.tl[t + 1] : (int64_t)nleaves;
+    moff[t] = (int32_t)P.tl[t];
+    if (!stack_leaf_dict(P.lv.data() + P.tl[t], present.data() + P.tl[t], (int)(l1 - P.tl[t]), nd->dict[t],
+                         map.data() + P.tl[t]))
+      return fail(SBAG_EINVAL, "NaN feature value");
+    const auto& d = nd->dict[t];
+    maxd = std::max(maxd, d.size());
+    const auto z = std::lower_bound(d.begin(), d.end(), 0.0);
+    if (z != d.end() && *z == 0.0) nd->zero_code[t] = (int)(z - d.begin());
+  }
+  nd->code_bytes = maxd <= 256 ? 1 : 2;  // (a tree of the tiled plan has fewer than 65536 leaves)
+  // pass 2: ordinals -> codes at the final width, padding columns included
+  const size_t bytes = (size_t)N * nd->S * nd->code_bytes;
+  HIP_TRY(hipMalloc(&nd->d_codes, bytes + 256));  // zero slack: k_hist_rl over-reads rows
+  HIP_TRY(hipMemsetAsync((uint8_t*)nd->d_codes + bytes, 0, 256, c->stream));
+  uint16_t* d_map;
+  int32_t* d_moff;
+  TRY(ws_typed(c, "stk_map", nleaves, &d_map));
+  TRY(ws_typed(c, "stk_moff", (size_t)K, &d_moff));
+  TRY(h2d(c, d_map, map.data(), nleaves));
+  TRY(h2d(c, d_moff, moff.data(), (size_t)K));
+  launch_stack_codes(c->stream, d_idx, N, K, nd->S, d_map, d_moff, nd->d_codes, nd->code_bytes);
+  HIP_TRY(hipGetLastError());
+  // the label column is ds's: its values, what analyze_labels found of them, and a copy of
+  // their fixed-point image made on the device (the new dataset owns it)
+  nd->lab = ds->lab;
+  nd->lab.d_labk = nullptr;
+  nd->lab.d_y64 = nullptr;  // (built by the first fit that needs it)
+  HIP_TRY(hipMalloc(&nd->lab.d_labk, (size_t)std::max<int64_t>(N, 1) * 4));
+  HIP_TRY(hipMemcpyAsync(nd->lab.d_labk, ds->lab.d_labk, (size_t)N * 4, hipMemcpyDeviceToDevice, c->stream));
+  TRY(upload_dict(nd.get()));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->pin_used = 0;
+  *out = nd.release();
   return SBAG_OK;
 }
 

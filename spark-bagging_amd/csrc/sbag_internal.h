@@ -402,6 +402,51 @@ void launch_predict_oob_perm(hipStream_t st, const PredictArgs& a, const OobArgs
 // codes [N][S] of code_bytes 1 / 2 / 4
 void launch_permute_column(hipStream_t st, void* dst, const void* orig, int code_bytes, int64_t N,
                            int32_t S, int32_t g, const int32_t* src);
+// ---- stacking (sbag_stack.hip): the level-1 dataset of a forest of base learners (feature k
+// of a row = base tree k's prediction) and the two-level transform, both in code space.
+// k_stack_walk: k_predict_tiled's geometry and plan (`a`; LDS = predict_tiled_lds with
+// a.agg = kAggMean); idx[t][row] = the index the row's leaf carries in tree t (its ordinal
+// among the tree's leaves, or the rank of its value: whatever the plan's leaf nodes hold), and
+// with `present` the leaf's flag present[tree_leaf[t] + index] |= 1 (LDS flags per chunk, in
+// the place of the leaf values, then one global atomic per newly reached leaf).
+void launch_stack_walk(hipStream_t st, const PredictArgs& a, uint16_t* idx, uint32_t* present);
+// k_stack_codes: out[row][k] = map[map_off[k] + idx[k][row]] for k < K, 0 for the padding
+// columns [K, S), at the final code width (1 or 2 bytes)
+void launch_stack_codes(hipStream_t st, const uint16_t* idx, int64_t N, int32_t K, int32_t S,
+                        const uint16_t* map, const int32_t* map_off, void* out, int code_bytes);
+// k_predict_stacked: the fused transform.  nodes: the base trees the stack tree tests, then the
+// stack tree, children adjacent, child links absolute.  A base leaf is 0x80000000 | rank of its
+// value among the tree's sorted distinct leaf values; a stack node's b is (slot << 17) | (tc + 1)
+// with root[slot] the root of the base tree it tests and tc the largest rank whose value is <=
+// its threshold; a stack leaf is 0x80000000 | index into leaves.
+struct StackArgs {
+  const void* codes;   // [N][S] u8 / u16
+  int32_t code_bytes, S;
+  int64_t N;
+  const PNode* nodes;
+  const double* leaves;
+  const int32_t* root;
+  int32_t nnodes, nleaves, nroot, sroot;  // sroot: the stack tree's root
+  double* out;
+};
+size_t predict_stacked_lds(const StackArgs& a);
+void launch_predict_stacked(hipStream_t st, const StackArgs& a);
+// the general path's second step: the stack tree over level-1 ranks [K][N] in global memory
+struct StackTopNode {
+  uint32_t a;    // internal: left child (right = a + 1); leaf: 0x80000000 | leaf index
+  uint32_t k;    // base tree tested
+  uint32_t cut;  // go left iff rank < cut
+  uint32_t pad;
+};
+void launch_stack_top(hipStream_t st, const StackTopNode* nodes, const double* leaves, const void* ranks,
+                      int rank_bytes /* 2 or 4 */, int64_t N, double* out);
+// k_stack_rank_walk: ranks[k][row] (u32) by a node walk from global memory (X fp64 rows, or
+// codes + dictionaries as launch_predict); a leaf's DevNode.pad is its ordinal in the tree, its
+// rank rank_tab[leaf_off[k] + pad]
+void launch_stack_rank_walk(hipStream_t st, const double* X, const void* codes, int code_bytes,
+                            const double* dict, const int64_t* dict_off, int64_t N, int32_t F, int32_t S,
+                            const DevNode* nodes, const int64_t* tree_off, int K, const uint32_t* rank_tab,
+                            const int64_t* leaf_off, uint32_t* ranks);
 // class-tile grouping of gini histogram entries (one workgroup per piece)
 // the grouping with known (segment, tile) sizes: cursors[q ntc + t] start at the tile's first
 // position and advance by atomics; pieces of tile_scatter_known_piece() entries
