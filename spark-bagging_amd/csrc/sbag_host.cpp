@@ -3885,6 +3885,8 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
   std::vector<int16_t> h_pos((size_t)R * Fmax, 0);
   uint8_t* cols_direct = nullptr;  // per-replica column copy written by the materialization
   int64_t cols_direct_npad = 0;    // (its row padding)
+  char bins_path[32] = "identity";    // SBAG_DEBUG_BINS: the binning kernel that ran,
+  const char* cols_from = "dataset";  // and where the column copy came from
   {
     int h = tm.begin(T_BIN);
     if (identity) {
@@ -3907,8 +3909,10 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
                       &d_cut, &d_z0));
       uint8_t* d_b;
       TRY(ws_typed(c, "bins", (size_t)N * S + 256, &d_b));
+      bool staged = false;
       launch_bin_cuts(c->stream, ds->d_codes, ds->code_bytes, N, ds->S, d_gsub, d_gF, F, 1, d_cut, ncp, d_z0,
-                      d_b, S, 0, nullptr, 0, 0, 0);
+                      d_b, S, 0, nullptr, 0, 0, 0, &staged);
+      snprintf(bins_path, sizeof bins_path, "shared %s", staged ? "cuts" : "rows");
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipMemsetAsync(d_b + (size_t)N * S, 0, 256, c->stream));  // zero slack
       d_bins = d_b;
@@ -3945,21 +3949,25 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
         uint8_t* d_c;
         const int64_t npad_c = (rows_b + 127) / 128 * 128;
         TRY(ws_typed(c, "cols", (size_t)R * ncol_r * npad_c, &d_c));
+        bool staged = false;
         if (ranked) {
+          int pieces = 0;
           if (!launch_bin_ranked(c->stream, ds->d_codes, ds->code_bytes, ds->S, entA, cap, d_inbag, capb, d_sub, d_Fr,
                                  Fmax, R, d_cut, ncp, d_z0, d_b, S, rows_b * S, d_c, ncol_r, npad_c,
-                                 (int64_t)ncol_r * npad_c))
+                                 (int64_t)ncol_r * npad_c, &pieces))
             return fail(SBAG_EDEVICE, "internal: ranked bins geometry");
+          snprintf(bins_path, sizeof bins_path, "ranked<%d>", pieces);
           HIP_TRY(hipGetLastError());
           launch_rank_entries(c->stream, entA, cap, d_inbag, R, capb);
           cols_direct = d_c;
           cols_direct_npad = npad_c;
         } else if (launch_bin_cuts(c->stream, ds->d_codes, ds->code_bytes, N, ds->S, d_sub, d_Fr, Fmax, R, d_cut,
                                    ncp, d_z0, d_b, S, (int64_t)N * S, d_c, ncol_r, npad_c,
-                                   (int64_t)ncol_r * npad_c)) {
+                                   (int64_t)ncol_r * npad_c, &staged)) {
           cols_direct = d_c;
           cols_direct_npad = npad_c;
         }
+        if (!ranked) snprintf(bins_path, sizeof bins_path, "%s", staged ? "cuts" : "rows");
       }
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipMemsetAsync(d_b + (size_t)R * rows_b * S, 0, 256, c->stream));  // zero slack
@@ -4008,7 +4016,9 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
       }
     } else {
       uint8_t* d_c = cols_direct;
+      cols_from = "binning";
       if (!d_c) {
+        cols_from = "transpose";
         TRY(ws_typed(c, "cols", (size_t)Rc * ncol * npad, &d_c));
         launch_transpose(c->stream, d_bins, N, S, ncol, d_c, npad, Rc, bins_rstride, cols_rstride);
         HIP_TRY(hipGetLastError());
@@ -4024,6 +4034,8 @@ static int fit_range_impl(sbag_ctx* c, sbag_dataset* ds, const sbag_fit_params* 
     }
     tm.end(h);
   }
+  if (getenv("SBAG_DEBUG_BINS"))
+    fprintf(stderr, "[sbag] bins: path %s cols %s replicas %d\n", bins_path, cols_from, bins_rstride ? R : 1);
   int32_t* d_nbins;
   TRY(ws_typed(c, "pos", h_pos.size(), &d_pos));
   TRY(ws_typed(c, "nbins", h_nbins.size(), &d_nbins));

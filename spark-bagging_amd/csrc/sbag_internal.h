@@ -264,12 +264,13 @@ struct SplitFindArgs {
 void launch_find_splits(hipStream_t st, const SplitFindArgs& a);
 // launch_bin_cuts over the in-bag rows only, by rank: out[r][rank][fl], cols[r][fl][rank] for the
 // ranks < inbag[r] of the replica's row-ordered entries ent[r][.] (capb >= every inbag[r]); false:
-// not supported for this geometry (the caller bins every row)
+// not supported for this geometry (the caller bins every row).  *pieces (diagnostics): the 16-byte
+// pieces of a code row per thread of the instance launched (k_bin_ranked<.,.,4 | 8 | 16>)
 bool launch_bin_ranked(hipStream_t st, const void* codes, int code_bytes, int32_t S_codes, const uint64_t* ent,
                        int64_t cap, const unsigned long long* d_inbag, int64_t capb, const int32_t* d_sub,
                        const int32_t* d_Fr, int32_t Fmax, int R, const uint32_t* d_cut, int32_t ncp,
                        const uint8_t* d_z0, uint8_t* out, int32_t S_out, int64_t out_rstride, uint8_t* cols,
-                       int32_t ncol, int64_t npad, int64_t cols_rstride);
+                       int32_t ncol, int64_t npad, int64_t cols_rstride, int* pieces = nullptr);
 // whether launch_bin_ranked takes this geometry (decided before the bins are sized)
 bool bin_ranked_fits(int code_bytes, int32_t S_codes, int32_t S_out, int32_t Fmax, int32_t ncp);
 // ent[r][i] row field := i (i < inbag[r])
@@ -279,11 +280,12 @@ void launch_rank_entries(hipStream_t st, uint64_t* ent, int64_t cap, const unsig
 // ascending, every cut >= 1, padded with ~0u; ncp a power of two) + z0[r][fl] (leading zero cuts
 // left out of the table; nullptr: none), zero past F_r; with cols the
 // column copy cols[r][fl < ncol][npad] is written by the same pass when the kernel can (returns
-// true; else the caller transposes)
+// true; else the caller transposes).  *staged (diagnostics): k_bin_cuts ran (false: its rows were
+// too wide for the staged tiles and k_bin_cuts_rows, a thread per row, ran instead)
 bool launch_bin_cuts(hipStream_t st, const void* codes, int code_bytes, int64_t N, int32_t S_codes,
                      const int32_t* d_sub, const int32_t* d_Fr, int32_t Fmax, int R, const uint32_t* d_cut,
                      int32_t ncp, const uint8_t* d_z0, uint8_t* out, int32_t S_out, int64_t out_rstride, uint8_t* cols, int32_t ncol,
-                     int64_t npad, int64_t cols_rstride);
+                     int64_t npad, int64_t cols_rstride, bool* staged = nullptr);
 void launch_compact(hipStream_t st, const uint8_t* counts, int64_t N, int R, const int32_t* d_labk,
                     uint64_t* ent, int64_t cap, unsigned long long* d_cursor,
                     unsigned long long* d_wsum, unsigned int* d_cmax, unsigned long long* d_sqsum);

@@ -3173,12 +3173,13 @@ template <typename CT>
 static bool launch_bin_cuts_any(hipStream_t st, const CT* codes, int64_t N, int32_t S_codes, const int32_t* d_sub,
                                 const int32_t* d_Fr, int32_t Fmax, int R, const uint32_t* d_cut, int32_t ncp,
                                 const uint8_t* d_z0, uint8_t* out, int32_t S_out, int64_t out_rstride,
-                                uint8_t* cols, int32_t ncol, int64_t npad, int64_t cols_rstride) {
+                                uint8_t* cols, int32_t ncol, int64_t npad, int64_t cols_rstride, bool* staged) {
   const bool ok = sizeof(CT) <= 2
                       ? launch_bin_cuts_t<CT, uint16_t>(st, codes, N, S_codes, d_sub, d_Fr, Fmax, R, d_cut, ncp, d_z0,
                                                         out, S_out, out_rstride, cols, ncol, npad, cols_rstride)
                       : launch_bin_cuts_t<CT, uint32_t>(st, codes, N, S_codes, d_sub, d_Fr, Fmax, R, d_cut, ncp, d_z0,
                                                         out, S_out, out_rstride, cols, ncol, npad, cols_rstride);
+  if (staged) *staged = ok;
   if (ok) return cols != nullptr;
   // rows too wide for the staged tiles: a thread per row (no column copy)
   const dim3 grid((unsigned)((N + 255) / 256), (unsigned)R);
@@ -3190,15 +3191,15 @@ static bool launch_bin_cuts_any(hipStream_t st, const CT* codes, int64_t N, int3
 bool launch_bin_cuts(hipStream_t st, const void* codes, int code_bytes, int64_t N, int32_t S_codes,
                      const int32_t* d_sub, const int32_t* d_Fr, int32_t Fmax, int R, const uint32_t* d_cut,
                      int32_t ncp, const uint8_t* d_z0, uint8_t* out, int32_t S_out, int64_t out_rstride,
-                     uint8_t* cols, int32_t ncol, int64_t npad, int64_t cols_rstride) {
+                     uint8_t* cols, int32_t ncol, int64_t npad, int64_t cols_rstride, bool* staged) {
   if (code_bytes == 1)
     return launch_bin_cuts_any(st, (const uint8_t*)codes, N, S_codes, d_sub, d_Fr, Fmax, R, d_cut, ncp, d_z0,
-                               out, S_out, out_rstride, cols, ncol, npad, cols_rstride);
+                               out, S_out, out_rstride, cols, ncol, npad, cols_rstride, staged);
   if (code_bytes == 2)
     return launch_bin_cuts_any(st, (const uint16_t*)codes, N, S_codes, d_sub, d_Fr, Fmax, R, d_cut, ncp, d_z0,
-                               out, S_out, out_rstride, cols, ncol, npad, cols_rstride);
+                               out, S_out, out_rstride, cols, ncol, npad, cols_rstride, staged);
   return launch_bin_cuts_any(st, (const uint32_t*)codes, N, S_codes, d_sub, d_Fr, Fmax, R, d_cut, ncp, d_z0,
-                             out, S_out, out_rstride, cols, ncol, npad, cols_rstride);
+                             out, S_out, out_rstride, cols, ncol, npad, cols_rstride, staged);
 }
 
 // k_bin_ranked: k_bin_cuts over a replica's in-bag rows only, stored by in-bag rank (the
@@ -3286,17 +3287,24 @@ __global__ __launch_bounds__(256) void k_bin_ranked(const CT* __restrict__ codes
     load_block(rows_next);  // the next block's code rows in flight
     rows_next = load_rows(n0 + 2 * kRows);
     block_sync();
+    int gcur = gv;
     for (int q = wave, j = 0; q < ngrp4; q += 4, j++) {
       if (4 * q >= fr) {
         *(uint32_t*)(sb + lane * pb + 4 * q) = 0u;
         continue;
+      }
+      // (a wave's 64 lanes hold the offsets of 16 of its groups: past 256 features the next
+      // 16 groups' are loaded -- lane l again holds feature 4 (q + 4 (l >> 2)) + (l & 3))
+      if (j && !(j & 15)) {
+        const int fl = min(4 * (q + 4 * (lane >> 2)) + (lane & 3), fr - 1);
+        gcur = sub[(int64_t)r * Fmax + fl] * (int)sizeof(CT);
       }
       const KT* ks[4];
       uint32_t cv[4], idx[4];
 #pragma unroll
       for (int k = 0; k < 4; k++) {
         const int fl = min(4 * q + k, fr - 1);
-        const int gb = __builtin_amdgcn_readlane(gv, 4 * j + k);
+        const int gb = __builtin_amdgcn_readlane(gcur, 4 * (j & 15) + k);
         ks[k] = sk + (size_t)fl * ncp;
         cv[k] = (uint32_t) * (const CT*)(sc + lane * pc + gb);
         idx[k] = 0u;
@@ -3402,7 +3410,7 @@ static bool launch_bin_ranked_t(hipStream_t st, const CT* codes, int32_t S_codes
                                 const unsigned long long* d_inbag, int64_t capb, const int32_t* d_sub,
                                 const int32_t* d_Fr, int32_t Fmax, int R, const uint32_t* d_cut, int32_t ncp,
                                 const uint8_t* d_z0, uint8_t* out, int32_t S_out, int64_t out_rstride, uint8_t* cols,
-                                int32_t ncol, int64_t npad, int64_t cols_rstride) {
+                                int32_t ncol, int64_t npad, int64_t cols_rstride, int* pieces) {
   constexpr int kRows = 64;
   if (!bin_ranked_fits((int)sizeof(CT), S_codes, S_out, Fmax, ncp) || npad % kRows != 0 || !cols) return false;
   const size_t lds = bin_ranked_lds((int)sizeof(CT), S_codes, S_out, Fmax, ncp);
@@ -3421,6 +3429,7 @@ static bool launch_bin_ranked_t(hipStream_t st, const CT* codes, int32_t S_codes
                     (void*)&cols,  (void*)&ncol,    (void*)&npad,  (void*)&cols_rstride, (void*)&rpc};
     (void)hipLaunchKernel(fn, g, dim3(256), args, lds, st);
   };
+  if (pieces) *pieces = rowb <= 256 ? 4 : rowb <= 512 ? 8 : 16;
   if (rowb <= 256)
     go((const void*)k_bin_ranked<CT, KT, 4>);
   else if (rowb <= 512)
@@ -3434,18 +3443,18 @@ bool launch_bin_ranked(hipStream_t st, const void* codes, int code_bytes, int32_
                        int64_t cap, const unsigned long long* d_inbag, int64_t capb, const int32_t* d_sub,
                        const int32_t* d_Fr, int32_t Fmax, int R, const uint32_t* d_cut, int32_t ncp,
                        const uint8_t* d_z0, uint8_t* out, int32_t S_out, int64_t out_rstride, uint8_t* cols,
-                       int32_t ncol, int64_t npad, int64_t cols_rstride) {
+                       int32_t ncol, int64_t npad, int64_t cols_rstride, int* pieces) {
   if (code_bytes == 1)
     return launch_bin_ranked_t<uint8_t, uint16_t>(st, (const uint8_t*)codes, S_codes, ent, cap, d_inbag, capb, d_sub,
                                                   d_Fr, Fmax, R, d_cut, ncp, d_z0, out, S_out, out_rstride, cols,
-                                                  ncol, npad, cols_rstride);
+                                                  ncol, npad, cols_rstride, pieces);
   if (code_bytes == 2)
     return launch_bin_ranked_t<uint16_t, uint16_t>(st, (const uint16_t*)codes, S_codes, ent, cap, d_inbag, capb,
                                                    d_sub, d_Fr, Fmax, R, d_cut, ncp, d_z0, out, S_out, out_rstride,
-                                                   cols, ncol, npad, cols_rstride);
+                                                   cols, ncol, npad, cols_rstride, pieces);
   return launch_bin_ranked_t<uint32_t, uint32_t>(st, (const uint32_t*)codes, S_codes, ent, cap, d_inbag, capb, d_sub,
                                                  d_Fr, Fmax, R, d_cut, ncp, d_z0, out, S_out, out_rstride, cols,
-                                                 ncol, npad, cols_rstride);
+                                                 ncol, npad, cols_rstride, pieces);
 }
 
 // entries' row field -> their in-bag rank (after k_bin_ranked)
