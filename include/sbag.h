@@ -388,6 +388,49 @@ int sbag_predict_oob_raw(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset
                          const sbag_sampler_params* sampler, const int64_t* partition_offsets,
                          int32_t num_partitions, int32_t kind, int32_t num_classes,
                          double* raw_out, int32_t* n_oob_out /* host [num_rows] or NULL */);
+/* ---- weighted sums over the trees: the transforms of the boosted model families.  out is
+ * host [num_rows x num_cols], row-major; weights is host [num_weights], weight t that of tree
+ * t; the trees are taken in forest order, one at a time, in sequential fp64.
+ *   SBAG_W_DOT    (a forest of any impurity; its tree count a multiple of num_cols)
+ *                 out[r][c] = 0.0 for every column; then for every tree t with
+ *                 t % num_cols == c: out[r][c] = out[r][c] + (tree_t(r) * weights[t]).  The
+ *                 product is rounded to fp64 before the addition: no FMA, no reassociation.
+ *                 num_cols == 1 is GBMRegressionModel.predict without its `+ const`
+ *                 (GBMRegressor.scala:511-516: BLAS.dot(predictions, weights)) and
+ *                 BoostingRegressionModel.predict without its `/ sumWeights`
+ *                 (BoostingRegressor.scala:403-405); num_cols == numClasses over trees laid
+ *                 out iteration-major (tree m * numClasses + k) is the `res` of
+ *                 GBMClassificationModel.predictRaw before its softmax
+ *                 (GBMClassifier.scala:539-547).
+ *   SBAG_W_CLASS  (a gini forest; num_cols >= sbag_forest_num_classes)
+ *                 out[r][c] = 0.0 for every column; then for every tree t:
+ *                 out[r][cls] = out[r][cls] + weights[t], cls the class tree_t(r) predicts.
+ *                 This is BoostingClassificationModel.predictRaw
+ *                 (tmp(model.predict(features).ceil.toInt) += 1.0 * weight,
+ *                 BoostingClassifier.scala:428-437).  A column no tree hits stays +0.0.
+ * The weights are taken as they come: negative, infinite and NaN weights follow IEEE
+ * arithmetic (where a NaN comes out is defined, its payload bits are not).  The softmax, the
+ * `+ const` and the `/ sumWeights` stay with the caller: one pass each over
+ * num_rows x num_cols values.  num_rows == 0 is SBAG_OK.
+ * SBAG_EINVAL (nothing written, the context stays usable): a null argument, an unknown kind,
+ * num_weights different from the forest's tree count, num_cols < 1, SBAG_W_DOT on a tree
+ * count that is no multiple of num_cols, SBAG_W_CLASS on a forest that is not gini or with
+ * num_cols below its class count, a subspace that reaches past num_features (or ds's
+ * features), ds on another device.
+ * u8 / u16 codes whose trees fit an LDS chunk beside num_cols x 512 fp64 accumulators go
+ * through one fused pass (host rows are binned against the forest's thresholds first, in row
+ * batches as in sbag_predict); u32 codes, larger trees, more columns, and every call under
+ * SBAG_WPRED_FORCE_FALLBACK=1 (read on every call) walk global memory, one thread per row:
+ * the same bits.                                                                       */
+#define SBAG_W_DOT 0   /* out[r][t % num_cols] += tree_t(r) * weights[t] */
+#define SBAG_W_CLASS 1 /* out[r][class tree_t(r) predicts] += weights[t] */
+int sbag_predict_weighted(sbag_ctx* ctx, const sbag_forest* f, const double* X, int64_t num_rows,
+                          int32_t num_features, int32_t kind,
+                          const double* weights /* host [num_weights] */, int32_t num_weights,
+                          int32_t num_cols, double* out /* host [num_rows x num_cols], row-major */);
+int sbag_predict_weighted_dataset(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* ds,
+                                  int32_t kind, const double* weights, int32_t num_weights,
+                                  int32_t num_cols, double* out);
 /* ---- Stacking: the level-1 dataset and the two-level transform -----------------------------
  * StackingRegressor.train (ml/regression/StackingRegressor.scala:163-171) and
  * StackingClassifier.train (ml/classification/StackingClassifier.scala:164-172) map every

@@ -18,6 +18,7 @@ IMPURITY_VARIANCE, IMPURITY_GINI = 0, 1
 AGG_MEAN, AGG_MODE = 0, 1
 OUT_SUM, OUT_VOTES = 2, 3  # device outputs of sbag_predict_dataset_device
 RAW_VOTES, RAW_LEAF = 0, 1  # kinds of sbag_predict_raw: hard / soft voting
+W_DOT, W_CLASS = 0, 1  # kinds of sbag_predict_weighted: weighted sums / class weights
 COL_F64, COL_F32, COL_U8 = 0, 1, 2  # sbag_dataset_create_columns
 
 # every symbol include/sbag.h declares (checked by tests/test_abi.py)
@@ -35,6 +36,7 @@ EXPORTED = [
     "sbag_predict_raw_dataset", "sbag_predict_oob_raw",
     "sbag_sample_boosted", "sbag_sample_boosted_stats", "sbag_fit_bag",
     "sbag_dataset_create_stacked", "sbag_predict_stacked", "sbag_predict_stacked_dataset",
+    "sbag_predict_weighted", "sbag_predict_weighted_dataset",
 ]
 
 
@@ -170,6 +172,8 @@ def lib():
             "sbag_predict_raw": [P, P, P, i64, i32, i32, i32, P],
             "sbag_predict_raw_dataset": [P, P, P, i32, i32, P],
             "sbag_predict_oob_raw": [P, P, P, ctypes.POINTER(SamplerParams), P, i32, i32, i32, P, P],
+            "sbag_predict_weighted": [P, P, P, i64, i32, i32, P, i32, i32, P],
+            "sbag_predict_weighted_dataset": [P, P, P, i32, P, i32, i32, P],
             "sbag_forest_timing": [P, ctypes.POINTER(Timing)],
             "sbag_predict": [P, P, P, i64, i32, i32, P, P],
             "sbag_predict_dataset": [P, P, P, i32, P],
@@ -698,6 +702,28 @@ def predict_oob_raw(ctx, forest, dataset, *, replacement, sample_ratio, seed, le
     check(lib().sbag_predict_oob_raw(ctx.handle, forest.handle, dataset.handle, ctypes.byref(p), ptr(off),
                                      P, kind, C, ptr(raw), ptr(n_oob)))
     return raw, n_oob
+
+
+def predict_weighted(ctx, forest, X, kind, weights, num_cols=1):
+    """Weighted sums over the trees of host rows (sbag_predict_weighted): fp64 [N, num_cols].
+    W_DOT: out[r, t % num_cols] += tree_t(r) * weights[t] in forest order, the product rounded
+    first; W_CLASS: out[r, class tree_t(r) predicts] += weights[t]."""
+    X = np.ascontiguousarray(X, np.float64)
+    w = np.ascontiguousarray(weights, np.float64).reshape(-1)
+    out = np.zeros((X.shape[0], max(int(num_cols), 0)), np.float64)
+    check(lib().sbag_predict_weighted(ctx.handle, forest.handle, ptr(X), X.shape[0], X.shape[1], kind,
+                                      ptr(w), len(w), int(num_cols), ptr(out)))
+    return out
+
+
+def predict_weighted_dataset(ctx, forest, dataset, kind, weights, num_cols=1):
+    """predict_weighted over a device dataset (sbag_predict_weighted_dataset): no feature
+    leaves the device."""
+    w = np.ascontiguousarray(weights, np.float64).reshape(-1)
+    out = np.zeros((dataset.shape[0], max(int(num_cols), 0)), np.float64)
+    check(lib().sbag_predict_weighted_dataset(ctx.handle, forest.handle, dataset.handle, kind, ptr(w),
+                                              len(w), int(num_cols), ptr(out)))
+    return out
 
 
 def predict_stacked(ctx, base, stack, X_or_dataset):

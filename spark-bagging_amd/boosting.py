@@ -114,18 +114,6 @@ def terminate(avgl, with_validation, error, verror, tol, num_round, num_try, it,
     return terminate_val(with_validation, error, verror, tol, num_round, num_try, it)
 
 
-def weighted_mean(per_tree, weights):
-    """BoostingRegressionModel.predict: BLAS.dot(predictions, weights) / weights.sum, both
-    left-to-right sums in booster order."""
-    acc = np.zeros(per_tree.shape[1])
-    wsum = 0.0
-    for p, w in zip(per_tree, weights):
-        acc = acc + p * w
-        wsum = wsum + w
-    with np.errstate(divide="ignore", invalid="ignore"):
-        return acc / np.float64(wsum)
-
-
 def _rows_and_ctx(dataset, device):
     if isinstance(dataset, nat.DeviceDataset):
         return dataset.features(), dataset.ctx
@@ -221,6 +209,19 @@ class _BoostingModel(_BoostingParams):
         _, pt = nat.predict(ctx, self.native_forest(), X, agg, per_tree=True)
         return pt, X.shape[0]
 
+    def _weighted(self, dataset, device, kind, num_cols):
+        """sbag_predict_weighted(_dataset) over the boosters and their weights, fp64
+        [N, num_cols]; a DeviceDataset stays resident.  (None, N) for a model without boosters."""
+        if isinstance(dataset, nat.DeviceDataset):
+            if not self.models:
+                return None, dataset.shape[0]
+            return nat.predict_weighted_dataset(dataset.ctx, self.native_forest(), dataset, kind,
+                                                self.weights, num_cols), dataset.shape[0]
+        X, ctx = _rows_and_ctx(dataset, device)
+        if not self.models:
+            return None, X.shape[0]
+        return nat.predict_weighted(ctx, self.native_forest(), X, kind, self.weights, num_cols), X.shape[0]
+
     def predict(self, features):
         return float(self.transform(np.asarray(features, np.float64)[None, :])[0])
 
@@ -278,8 +279,16 @@ class BoostingRegressionModel(_BoostingModel):
                        loss=lambda x: str(x).lower() in REGRESSOR_LOSSES)
 
     def transform(self, dataset, device=0):
-        pt, _ = self.per_tree(dataset, device)
-        return weighted_mean(pt, self.weights)
+        """BLAS.dot(predictions, weights) / weights.sum: the dot in booster order on the device
+        (sbag_predict_weighted, W_DOT with one column), the weights' left-to-right sum and the
+        division here."""
+        acc, n = self._weighted(dataset, device, nat.W_DOT, 1)
+        acc = np.zeros(n) if acc is None else acc[:, 0]
+        wsum = 0.0
+        for w in self.weights:
+            wsum = wsum + w
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return acc / np.float64(wsum)
 
     @classmethod
     def load(cls, path):
@@ -303,14 +312,11 @@ class BoostingClassificationModel(_BoostingModel):
         self.numClasses = int(num_classes)
 
     def predict_raw(self, dataset, device=0):
-        """tmp(model.predict(features).ceil.toInt) += 1.0 * weight, in booster order."""
-        pt, n = self.per_tree(dataset, device)
-        raw = np.zeros((n, self.numClasses))
-        rows = np.arange(n)
-        for p, w in zip(pt, self.weights):
-            k = np.ceil(p).astype(np.int64)
-            raw[rows, k] = raw[rows, k] + 1.0 * w
-        return raw
+        """tmp(model.predict(features).ceil.toInt) += 1.0 * weight, in booster order, on the
+        device in the pass that walks the trees (sbag_predict_weighted, W_CLASS: a gini leaf
+        predicts an integral class id, and 1.0 * weight is weight)."""
+        raw, n = self._weighted(dataset, device, nat.W_CLASS, self.numClasses)
+        return np.zeros((n, self.numClasses)) if raw is None else raw
 
     def transform(self, dataset, device=0):
         """ClassificationModel.raw2prediction: rawPrediction.argmax (the first maximum)."""

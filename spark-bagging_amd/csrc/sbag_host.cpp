@@ -5541,7 +5541,173 @@ static int raw_prepare(sbag_ctx* c, const sbag_forest* f, int kind, int code_byt
   return SBAG_OK;
 }
 
+// ---- weighted sums over the trees (sbag_wpred.hip).  A call goes through k_wpred_tiled when
+// plan_tiled holds the forest beside the accumulators (u8 / u16 codes, every tree within the
+// chunk, num_cols columns of 512 doubles within the LDS) and SBAG_WPRED_FORCE_FALLBACK is
+// not set (read on every call), else through k_wpred_walk.
+static int check_weighted(const sbag_forest* f, int kind, int32_t num_weights, int32_t num_cols) {
+  const int L = (int)f->trees.size();
+  if (kind != SBAG_W_DOT && kind != SBAG_W_CLASS) return fail(SBAG_EINVAL, "unknown weighted prediction kind");
+  if (num_weights != L)
+    return fail(SBAG_EINVAL, std::to_string(num_weights) + " weights for a forest of " + std::to_string(L) + " trees");
+  if (num_cols < 1) return fail(SBAG_EINVAL, "num_cols must be at least 1");
+  if (kind == SBAG_W_DOT && L % num_cols != 0)
+    return fail(SBAG_EINVAL, "the forest's " + std::to_string(L) + " trees are no multiple of num_cols " +
+                                 std::to_string(num_cols));
+  if (kind == SBAG_W_CLASS) {
+    if (f->impurity != SBAG_IMPURITY_GINI || f->nclasses <= 0 || f->nclasses > 4096)
+      return fail(SBAG_EINVAL, "class weights need a gini forest");
+    if (num_cols < f->nclasses)
+      return fail(SBAG_EINVAL, "num_cols " + std::to_string(num_cols) + " is below the forest's " +
+                                   std::to_string(f->nclasses) + " classes");
+  }
+  return SBAG_OK;
+}
+
+struct WpredRun {
+  bool tiled = false;
+  PredictArgs pa{};                // tiled: the uploaded plan (codes / N set per launch)
+  const DevNode* nodes = nullptr;  // general path
+  const int64_t* off = nullptr;
+  WpredArgs q{};
+};
+
+// the plan of a weighted pass over codes of `code_bytes` at row stride S (tc_of: a threshold
+// in code space, as plan_tiled's), uploaded with the weights; may_tile false: the general path
+template <typename TC>
+static int wpred_prepare(sbag_ctx* c, const sbag_forest* f, int kind, const double* weights, int num_cols,
+                         int code_bytes, int S, int F, bool may_tile, TC tc_of, WpredRun& R) {
+  const int L = (int)f->trees.size();
+  const char* ffb = getenv("SBAG_WPRED_FORCE_FALLBACK");
+  if (ffb && atoi(ffb) != 0) may_tile = false;
+  R.pa.code_bytes = code_bytes;
+  R.pa.S = S;
+  R.pa.agg = kAggMean;  // predict_tiled_lds: the row tile and the chunk; the accumulators are extra
+  TiledPlan P;
+  R.tiled = may_tile && plan_tiled(f, R.pa, F, tc_of, P, wpred_acc_lds(num_cols));
+  double* d_w;
+  TRY(ws_typed(c, "pw_weights", (size_t)L, &d_w));
+  TRY(h2d(c, d_w, weights, (size_t)L));
+  R.q.kind = kind;
+  R.q.C = num_cols;
+  R.q.weights = d_w;
+  if (R.tiled) {
+    if (kind == SBAG_W_DOT)  // a leaf carries its product, rounded here once (no FMA: a lone multiplication)
+      for (int t = 0; t < L; t++) {
+        const int64_t l1 = t + 1 < L ? P.tl[t + 1] : (int64_t)P.lv.size();
+        for (int64_t l = P.tl[t]; l < l1; l++) P.lv[l] = P.lv[l] * weights[t];
+      }
+    return upload_plan(c, P, R.pa);
+  }
+  return upload_forest(c, f, &R.nodes, &R.off);
+}
+
 extern "C" {
+
+int sbag_predict_weighted(sbag_ctx* c, const sbag_forest* f, const double* X, int64_t N, int32_t F,
+                          int32_t kind, const double* weights, int32_t num_weights, int32_t num_cols,
+                          double* out) {
+  if (!c || !f || !X || !weights || !out || N < 0 || F <= 0) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(check_weighted(f, kind, num_weights, num_cols));
+  for (const HTree& t : f->trees)
+    for (int32_t g : t.sub)
+      if (g >= F) return fail(SBAG_EINVAL, "feature vector shorter than a subspace index");
+  if (N == 0) return SBAG_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const int L = (int)f->trees.size();
+  // rows are binned on the device against the forest's own thresholds, as in sbag_predict
+  std::vector<std::vector<double>> T(F);
+  for (const HTree& t : f->trees)
+    for (const sbag_node& n : t.nodes)
+      if (n.left >= 0) T[t.sub[n.feature]].push_back(n.threshold);
+  std::vector<int64_t> toff(F + 1, 0);
+  size_t max_thr = 0;
+  for (int g = 0; g < F; g++) {
+    std::sort(T[g].begin(), T[g].end());
+    T[g].erase(std::unique(T[g].begin(), T[g].end()), T[g].end());
+    toff[g + 1] = toff[g] + (int64_t)T[g].size();
+    max_thr = std::max(max_thr, T[g].size());
+  }
+  const int32_t Sq = (F + 15) / 16 * 16;
+  WpredRun R;
+  TRY(wpred_prepare(c, f, kind, weights, num_cols, 2, Sq, F, max_thr <= 65535, [&](int g, double thr) {
+    return (int64_t)(std::lower_bound(T[g].begin(), T[g].end(), thr) - T[g].begin());
+  }, R));
+  double* d_out;
+  TRY(ws_typed(c, "pwout", (size_t)N * num_cols, &d_out));
+  double* d_X;
+  if (R.tiled) {
+    std::vector<double> tv((size_t)std::max<int64_t>(toff[F], 1));
+    for (int g = 0; g < F; g++) std::copy(T[g].begin(), T[g].end(), tv.begin() + toff[g]);
+    double* d_T;
+    int64_t* d_toff;
+    TRY(ws_typed(c, "pq_thr", tv.size(), &d_T));
+    TRY(ws_typed(c, "pq_off", toff.size(), &d_toff));
+    TRY(h2d(c, d_T, tv.data(), tv.size()));
+    TRY(h2d(c, d_toff, toff.data(), toff.size()));
+    int64_t batch = std::max<int64_t>(1, std::min<int64_t>(N, ((int64_t)2 << 30) / (8 * (int64_t)F)));
+    if (const char* e = getenv("SBAG_PREDICT_BATCH_ROWS")) batch = std::max<int64_t>(1, std::min<int64_t>(batch, atoll(e)));
+    uint16_t* d_codes;
+    TRY(ws_typed(c, "pX", (size_t)batch * F, &d_X));
+    TRY(ws_typed(c, "pq_codes", (size_t)batch * Sq, &d_codes));
+    for (int64_t r0 = 0; r0 < N; r0 += batch) {
+      const int64_t n = std::min(batch, N - r0);
+      HIP_TRY(hipMemcpyAsync(d_X, X + r0 * F, (size_t)n * F * 8, hipMemcpyHostToDevice, c->stream));
+      launch_quantize(c->stream, d_X, n, F, d_T, d_toff, d_codes, Sq);
+      R.pa.codes = d_codes;
+      R.pa.N = n;
+      R.q.out = d_out + r0 * num_cols;
+      launch_wpred_tiled(c->stream, R.pa, R.q);
+      HIP_TRY(hipGetLastError());
+    }
+  } else {
+    TRY(ws_typed(c, "pX", (size_t)N * F, &d_X));
+    TRY(h2d(c, d_X, X, (size_t)N * F));
+    R.q.out = d_out;
+    launch_wpred_walk(c->stream, d_X, nullptr, 1, nullptr, nullptr, N, F, F, R.nodes, R.off, L, R.q);
+    HIP_TRY(hipGetLastError());
+  }
+  TRY(d2h(c, out, d_out, (size_t)N * num_cols));
+  return SBAG_OK;
+}
+
+int sbag_predict_weighted_dataset(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds, int32_t kind,
+                                  const double* weights, int32_t num_weights, int32_t num_cols,
+                                  double* out) {
+  if (!c || !f || !ds || !weights || !out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(check_weighted(f, kind, num_weights, num_cols));
+  for (const HTree& t : f->trees)
+    for (int32_t g : t.sub)
+      if (g >= ds->F) return fail(SBAG_EINVAL, "dataset has fewer features than the model");
+  if (ds->ctx->device != c->device)
+    return fail(SBAG_EINVAL, "dataset lives on device " + std::to_string(ds->ctx->device) +
+                                 ", the context on device " + std::to_string(c->device));
+  if (ds->N == 0) return SBAG_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  WpredRun R;
+  // TreePoint's `value <= threshold` in the dataset's code space (dict sorted ascending)
+  TRY(wpred_prepare(c, f, kind, weights, num_cols, ds->code_bytes, ds->S, ds->F, ds->code_bytes != 4,
+                    [&](int g, double thr) {
+                      const std::vector<double>& d = ds->dict[g];
+                      return (int64_t)(std::upper_bound(d.begin(), d.end(), thr) - d.begin()) - 1;
+                    }, R));
+  double* d_out;
+  TRY(ws_typed(c, "pwout", (size_t)ds->N * num_cols, &d_out));
+  R.q.out = d_out;
+  if (R.tiled) {
+    R.pa.codes = ds->d_codes;
+    R.pa.N = ds->N;
+    launch_wpred_tiled(c->stream, R.pa, R.q);
+  } else {
+    launch_wpred_walk(c->stream, nullptr, ds->d_codes, ds->code_bytes, ds->d_dict, ds->d_dict_off, ds->N,
+                      ds->F, ds->S, R.nodes, R.off, (int)f->trees.size(), R.q);
+  }
+  HIP_TRY(hipGetLastError());
+  TRY(d2h(c, out, d_out, (size_t)ds->N * num_cols));
+  return SBAG_OK;
+}
 
 int sbag_predict_raw(sbag_ctx* c, const sbag_forest* f, const double* X, int64_t N, int32_t F,
                      int32_t kind, int32_t num_classes, double* raw_out) {

@@ -379,6 +379,28 @@ void launch_proba_walk(hipStream_t st, const double* X, const void* codes, int c
                        const double* dict, const int64_t* dict_off, int64_t N, int32_t F, int32_t S,
                        const DevNode* nodes, const int64_t* tree_off, const double* frac,
                        const int64_t* leaf_off, const ProbaArgs& q);
+// ---- weighted sums over the trees (sbag_wpred.hip): out[row][c] = +0.0, then for every tree
+// t in forest order
+//   kWDot    out[row][t % C] += tree_t(row) * weights[t]  (the product rounded, then added)
+//   kWClass  out[row][class tree_t(row) predicts] += weights[t]
+constexpr int kWDot = 0, kWClass = 1;
+struct WpredArgs {
+  int32_t kind;           // kWDot / kWClass
+  int32_t C;              // columns of out (kWClass: >= the forest's class count)
+  const double* weights;  // [L] on the device
+  double* out;            // [N][C], row-major
+};
+// LDS of k_wpred_tiled past predict_tiled_lds(agg = kAggMean): its accumulators fp64 [C][512]
+size_t wpred_acc_lds(int C);
+// k_wpred_tiled: k_proba_tiled's geometry over the plain plan (one value per leaf).  kWDot:
+// the plan's leaf values are the products prediction * weights[t] already (q.weights unused);
+// kWClass: the class ids
+void launch_wpred_tiled(hipStream_t st, const PredictArgs& a, const WpredArgs& q);
+// k_wpred_walk: one thread per row over DevNodes in global memory (X fp64 rows, or codes +
+// dictionaries as launch_predict)
+void launch_wpred_walk(hipStream_t st, const double* X, const void* codes, int code_bytes,
+                       const double* dict, const int64_t* dict_off, int64_t N, int32_t F, int32_t S,
+                       const DevNode* nodes, const int64_t* tree_off, int L, const WpredArgs& q);
 // ---- out-of-bag predictions under permuted features (sbag_oobperm.hip): slot k of a
 // feature batch is sbag_predict_oob with feature feat[k] of row r taken from row src[k][r].
 // Between learner batches a slot's state lives in global memory as the baseline's does:

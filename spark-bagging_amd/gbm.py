@@ -167,28 +167,14 @@ class GBMRegressionModel(_GBMParams):
         return self._forest
 
     def transform(self, dataset, device=0):
-        """predict = BLAS.dot(booster predictions, weights) + const per row: the trees are
-        walked on the device (k_predict_tiled, per-tree outputs), the dot is F2J ddot's
-        left-to-right sum of rounded products."""
+        """predict = BLAS.dot(booster predictions, weights) + const per row: F2J ddot's
+        left-to-right sum of rounded products, made on the device in the pass that walks the
+        trees (sbag_predict_weighted, W_DOT with one column); a DeviceDataset stays resident."""
         if not self.models:
             n = dataset.shape[0] if isinstance(dataset, nat.DeviceDataset) else len(dataset)
             return np.full(n, 0.0 + self.const)
-        if isinstance(dataset, nat.DeviceDataset):
-            X = dataset.features()
-            ctx = dataset.ctx
-        else:
-            X = dataset.features if isinstance(dataset, Frame) else dataset
-            ctx = nat.default_context(device)
-        if is_sparse(X):
-            X = X.toarray() if hasattr(X, "toarray") else X.to_dense()
-        X = np.asarray(X, np.float64)
-        if X.ndim == 1:
-            X = X[None, :]
-        _, per_tree = nat.predict(ctx, self.native_forest(), X, nat.AGG_MEAN, per_tree=True)
-        s = np.zeros(X.shape[0])
-        for p, w in zip(per_tree, self.weights):
-            s = s + p * w
-        return s + self.const
+        rows, ctx = _rows_and_ctx(dataset, device)
+        return _weighted(ctx, self.native_forest(), rows, self.weights, 1)[:, 0] + self.const
 
     def predict(self, features):
         return float(self.transform(np.asarray(features, np.float64)[None, :])[0])
@@ -458,16 +444,13 @@ class GBMClassificationModel(_GBMParams):
         return self._forest
 
     def raw_sums(self, X, ctx):
-        """res[:, k] = sum over m (in order) of models[m][k].predict * weights[m][k]."""
-        res = np.zeros((X.shape[0], self.numClasses))
+        """res[:, k] = sum over m (in order) of models[m][k].predict * weights[m][k], X host
+        rows or a DeviceDataset: sbag_predict_weighted, W_DOT with numClasses columns over the
+        iteration-major forest."""
         if not self.models:
-            return res
-        _, pt = nat.predict(ctx, self.native_forest(), X, nat.AGG_MEAN, per_tree=True)
-        K = self.numClasses
-        for m in range(len(self.models)):
-            for k in range(K):
-                res[:, k] = res[:, k] + pt[m * K + k] * self.weights[m][k]
-        return res
+            return np.zeros((X.shape[0], self.numClasses))
+        return _weighted(ctx, self.native_forest(), X, [w for ws in self.weights for w in ws],
+                         self.numClasses)
 
     def predict_raw(self, dataset, device=0):
         X, ctx = _rows_and_ctx(dataset, device)
@@ -531,15 +514,23 @@ class GBMClassificationModel(_GBMParams):
 
 
 def _rows_and_ctx(dataset, device):
+    """(a DeviceDataset as it is, or dense fp64 rows [N, F]; the context to run on)."""
     if isinstance(dataset, nat.DeviceDataset):
-        return dataset.features(), dataset.ctx
+        return dataset, dataset.ctx
     X = dataset.features if isinstance(dataset, Frame) else dataset
     if is_sparse(X):
-        X = X.toarray()
+        X = X.toarray() if hasattr(X, "toarray") else X.to_dense()
     X = np.asarray(X, np.float64)
     if X.ndim == 1:
         X = X[None, :]
     return X, nat.default_context(device)
+
+
+def _weighted(ctx, forest, rows, weights, num_cols):
+    """sbag_predict_weighted(_dataset), W_DOT: fp64 [N, num_cols]."""
+    if isinstance(rows, nat.DeviceDataset):
+        return nat.predict_weighted_dataset(ctx, forest, rows, nat.W_DOT, weights, num_cols)
+    return nat.predict_weighted(ctx, forest, rows, nat.W_DOT, weights, num_cols)
 
 
 class GBMClassifier(GBMRegressor):
