@@ -348,6 +348,56 @@ int sbag_predict_oob_permuted(sbag_ctx* ctx, const sbag_forest* f, const sbag_da
                               double* out /* host [num_perm x num_rows] */,
                               double* base_out /* host [num_rows] or NULL */,
                               int32_t* n_oob_out /* host [num_rows] or NULL */);
+/* ---- staged evaluation: the score of the forest's first l + 1 trees, for every l, in one
+ * pass (the out-of-bag error as a function of the number of trees: randomForest's plot(rf),
+ * GBTRegressionModel.evaluateEachIteration).  out is host [trees]; stage l (0-based) is the
+ * ensemble of trees [0, l].
+ * With a sampler (`ds`, `sampler`, `partition_offsets` as in sbag_predict_oob: the fit's),
+ * n_oob_l[r] counts the learners i <= l with counts[i][r] == 0 and pred_l[r] is
+ * sbag_predict_oob's aggregation over those learners only, in learner order:
+ *   SBAG_AGG_MEAN  s = 0.0; s = s + tree_i(r); pred_l = s / (double)n_oob_l
+ *   SBAG_AGG_MODE  breeze's mode of the prefix's out-of-bag votes: the first class to reach
+ *                  the prefix's maximum count
+ * With sampler == NULL no learner is masked: every row is covered from stage 0,
+ * n_oob_l = l + 1, and partition_offsets / num_partitions are ignored (the held-out curve,
+ * evaluateEachIteration on a validation dataset).  y is the dataset's label column
+ * (sbag_dataset_set_labels replaces it).
+ * The order of the two fp64 sums is part of the interface:
+ *   - per row, e = pred_l - y, se = e * e and ae = fabs(e), each rounded on its own; a row
+ *     that is not covered, or that lies past num_rows, contributes +0.0;
+ *   - rows fall into tiles of 512 consecutive rows, tile k holding rows [512k, 512k + 512);
+ *   - a tile's 512 terms are summed by halving: for h = 256, 128, ..., 1,
+ *     v[i] = v[i] + v[i + h] for i < h; the tile sum is v[0];
+ *   - the stage sum starts at 0.0 and adds the tile sums in tile order, left to right;
+ *   - no product or sum is contracted or reassociated;
+ *   - the order does not depend on learner batches, on how the forest is staged on the
+ *     device, or on which path ran.
+ * covered and correct are integers: any order gives the same value.
+ * Validation and error codes are sbag_predict_oob's: the sampler's learner range must hold as
+ * many learners as the forest has trees, SBAG_AGG_MODE needs class-valued trees, the
+ * dataset must live on the context's device and hold every feature a subspace names, a
+ * Poisson draw above 255 fails as in a fit, and SBAG_AGG_MODE over several learner batches
+ * with more than 256 MB of carried class counters is SBAG_EUNSUPPORTED.  A null ctx, f, ds
+ * or out is SBAG_EINVAL.  num_rows == 0 is SBAG_OK with every stage zeroed.  After any
+ * refusal nothing is written and the context stays usable.
+ * u8 / u16 datasets whose trees fit the LDS go through one fused pass; u32 codes, trees
+ * past the LDS chunk, more classes than the LDS counters hold, and every call under
+ * SBAG_STAGED_FORCE_FALLBACK=1 (read on every call) take the learners' per-tree
+ * predictions from the global-memory walk: the same bytes, slower.  Learner batches as in
+ * sbag_predict_oob (SBAG_OOB_BATCH_LEARNERS forces their size).  Only the trees x 32 bytes
+ * of out come down from the device. */
+typedef struct {
+  int64_t covered;  /* rows r with n_oob_l[r] >= 1                                   */
+  int64_t correct;  /* SBAG_AGG_MODE: covered rows whose stage prediction == label;
+                       SBAG_AGG_MEAN: 0                                              */
+  double  sum_se;   /* SBAG_AGG_MEAN: sum over covered rows of e*e, e = pred_l - y;
+                       SBAG_AGG_MODE: 0.0                                            */
+  double  sum_ae;   /* SBAG_AGG_MEAN: sum over covered rows of |e|; MODE: 0.0        */
+} sbag_stage_stats;
+int sbag_eval_staged(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* ds,
+                     const sbag_sampler_params* sampler /* or NULL */,
+                     const int64_t* partition_offsets, int32_t num_partitions, int32_t agg,
+                     sbag_stage_stats* out /* host [trees] */);
 /* ---- per-class raw predictions of a gini forest (ProbabilisticClassificationModel's
  * rawPrediction; neither kind is normalised).  raw_out is host [num_rows x num_classes],
  * row-major; the aggregated trees of a row are all of the forest's (sbag_predict_raw,

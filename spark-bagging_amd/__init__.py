@@ -13,7 +13,7 @@ from .ml import (BaggingClassificationModel, BaggingClassifier, BaggingRegressio
                  BaggingRegressor, DecisionTreeClassifier, DecisionTreeModel,
                  DecisionTreeRegressor, Frame, even_partitions, java_string_hash, oob_metrics,
                  oob_log_loss, oob_permutation_importance, permutation_source_rows,
-                 raw_to_probability)
+                 raw_to_probability, staged_metrics)
 from .gbm import (GBMClassificationModel, GBMClassifier, GBMRegressionModel,  # noqa: F401
                   GBMRegressor)
 from .boosting import (BoostingClassificationModel, BoostingClassifier,  # noqa: F401

@@ -36,7 +36,7 @@ EXPORTED = [
     "sbag_predict_raw_dataset", "sbag_predict_oob_raw",
     "sbag_sample_boosted", "sbag_sample_boosted_stats", "sbag_fit_bag",
     "sbag_dataset_create_stacked", "sbag_predict_stacked", "sbag_predict_stacked_dataset",
-    "sbag_predict_weighted", "sbag_predict_weighted_dataset",
+    "sbag_predict_weighted", "sbag_predict_weighted_dataset", "sbag_eval_staged",
 ]
 
 
@@ -111,6 +111,9 @@ class BoostedStats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "pad_"}
 
 
+# sbag_stage_stats: one record per stage of sbag_eval_staged
+STAGE_DTYPE = np.dtype([("covered", "<i8"), ("correct", "<i8"), ("sum_se", "<f8"), ("sum_ae", "<f8")])
+
 NODE_DTYPE = np.dtype([("id", "<i4"), ("left", "<i4"), ("right", "<i4"), ("feature", "<i4"),
                        ("split_bin", "<i4"), ("pad", "<i4"), ("threshold", "<f8"),
                        ("prediction", "<f8"), ("impurity", "<f8"), ("gain", "<f8")])
@@ -181,6 +184,7 @@ def lib():
             "sbag_predict_dataset_device": [P, P, P, i32, i32, P],
             "sbag_aggregate_device": [P, P, i32, i32, i64, i32, i32, i32, P],
             "sbag_predict_oob": [P, P, P, ctypes.POINTER(SamplerParams), P, i32, i32, P, P],
+            "sbag_eval_staged": [P, P, P, ctypes.POINTER(SamplerParams), P, i32, i32, P],
             "sbag_predict_oob_permuted": [P, P, P, ctypes.POINTER(SamplerParams), P, i32, i32, P, i32, P, P,
                                           P, P],
         }
@@ -634,6 +638,30 @@ def predict_oob(ctx, forest, dataset, *, replacement, sample_ratio, seed, learne
     check(lib().sbag_predict_oob(ctx.handle, forest.handle, dataset.handle, ctypes.byref(p), ptr(off),
                                  P, agg, ptr(out), ptr(n_oob)))
     return out, n_oob
+
+
+def eval_staged(ctx, forest, dataset, *, agg, replacement=None, sample_ratio=None, seed=None,
+                learner_begin=None, learner_end=None, partition_offsets=None):
+    """Staged evaluation (sbag_eval_staged): a structured array [trees] (STAGE_DTYPE: covered,
+    correct, sum_se, sum_ae), record l the score of the forest's first l + 1 trees against the
+    dataset's labels.  With the fit's sampler arguments (predict_oob's) every stage is the
+    out-of-bag one; with all of them None no learner is masked (the held-out curve) and
+    partition_offsets is ignored."""
+    sampler = (replacement, sample_ratio, seed, learner_begin, learner_end)
+    p = None
+    if any(a is not None for a in sampler):
+        if any(a is None for a in sampler):
+            raise IllegalArgumentException(SBAG_EINVAL, "give every sampler argument or none")
+        p = SamplerParams(int(replacement), 0, float(sample_ratio), int(seed), learner_begin, learner_end)
+    off = None
+    P = 1
+    if p is not None and partition_offsets is not None:
+        off = np.ascontiguousarray(partition_offsets, np.int64)
+        P = len(off) - 1
+    out = np.zeros(len(forest), STAGE_DTYPE)
+    check(lib().sbag_eval_staged(ctx.handle, forest.handle, dataset.handle,
+                                 ctypes.byref(p) if p is not None else None, ptr(off), P, agg, ptr(out)))
+    return out
 
 
 def predict_oob_permuted(ctx, forest, dataset, *, replacement, sample_ratio, seed, learner_begin, learner_end,

@@ -5449,6 +5449,155 @@ int sbag_predict_oob(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds,
   return SBAG_OK;
 }
 
+// Staged evaluation (sbag_staged.hip): sbag_predict_oob's validation, sampler, learner
+// batches and carried state, with the per-stage statistics taken on the device after every
+// tree.  sp == nullptr: no mask (no counts, one batch on the fused path).  The fused pass
+// parks kStagedMaxGroup stages per reduction when plan_tiled holds the park beside a chunk,
+// else one; where it refuses both, and under SBAG_STAGED_FORCE_FALLBACK=1 (read on every
+// call), the batch's per-tree predictions of k_predict go through k_staged_agg.
+int sbag_eval_staged(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds,
+                     const sbag_sampler_params* sp, const int64_t* partition_offsets, int32_t P,
+                     int32_t agg, sbag_stage_stats* out) {
+  static_assert(sizeof(sbag_stage_stats) == sizeof(StageStats) && offsetof(sbag_stage_stats, sum_ae) == 24,
+                "sbag_stage_stats is the kernels' StageStats");
+  if (!c || !f || !ds || !out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  if (sp) TRY(check_sampler(sp));
+  TRY(check_agg(f, agg));
+  const int L = (int)f->trees.size();
+  if (L == 0) return fail(SBAG_EINVAL, "the forest has no trees");
+  if (sp && sp->learner_end - sp->learner_begin != L)
+    return fail(SBAG_EINVAL, "the sampler's learner range holds " +
+                                 std::to_string(sp->learner_end - sp->learner_begin) +
+                                 " learners, the forest " + std::to_string(L) + " trees");
+  const int64_t N = ds->N;
+  std::vector<int64_t> poff;
+  if (sp) {
+    if (partition_offsets && P >= 1 && partition_offsets[P] != N)
+      return fail(SBAG_EINVAL, "partition_offsets must end at the dataset's row count");
+    TRY(check_partitions(P, partition_offsets, N, poff));
+  }
+  for (const HTree& t : f->trees)
+    for (int32_t g : t.sub)
+      if (g >= ds->F) return fail(SBAG_EINVAL, "dataset has fewer features than the model");
+  if (ds->ctx->device != c->device)
+    return fail(SBAG_EINVAL, "dataset lives on device " + std::to_string(ds->ctx->device) +
+                                 ", the context on device " + std::to_string(c->device));
+  if ((int64_t)ds->lab.y.size() != N) return fail(SBAG_EINVAL, "the dataset holds no label column");
+  if (N == 0) {
+    std::fill(out, out + L, sbag_stage_stats{0, 0, 0.0, 0.0});
+    return SBAG_OK;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  const int ncls = std::max(f->nclasses, 1);
+  const bool mode_agg = agg == SBAG_AGG_MODE;
+  const char* ff = getenv("SBAG_STAGED_FORCE_FALLBACK");
+  const bool may_tile = ds->code_bytes != 4 && !(ff && atoi(ff) == 1);
+  PredictArgs pa{};
+  TiledPlan Pl;
+  bool tiled = false;
+  StagedArgs sa{};
+  sa.trees = L;
+  sa.G = kStagedMaxGroup;
+  for (int G : {kStagedMaxGroup, 1}) {
+    if (!may_tile || tiled) break;
+    pa = PredictArgs{};
+    pa.code_bytes = ds->code_bytes;
+    pa.S = ds->S;
+    pa.N = N;
+    pa.agg = agg;
+    Pl = TiledPlan{};
+    sa.G = G;
+    tiled = plan_tiled(f, pa, ds->F, [&](int g, double thr) {
+      const std::vector<double>& d = ds->dict[g];
+      return (int64_t)(std::upper_bound(d.begin(), d.end(), thr) - d.begin()) - 1;
+    }, Pl, staged_park_lds(agg, G));
+  }
+  if (!tiled) sa.G = kStagedMaxGroup;  // (k_staged_agg's park is static)
+  // bytes per learner of a batch: its counts row (with a mask), and the fallback's fp64 predictions
+  const double per = (double)N * ((sp ? 1.0 : 0.0) + (tiled ? 0.0 : 8.0));
+  int batch = per > 0 ? (int)std::max(1.0, std::min((double)L, std::floor(bins_budget(c) / per))) : L;
+  if (const char* e = getenv("SBAG_OOB_BATCH_LEARNERS")) batch = std::max(1, std::min(L, atoi(e)));
+  const bool several = batch < L;
+  // mode counters in global memory, as sbag_predict_oob's; the fallback's row ranges hold
+  // whole 512-row tiles
+  int64_t gcnt_rows = 0;
+  if (mode_agg && (several || !tiled)) {
+    const int64_t cap_rows = std::max<int64_t>(512, ((int64_t)256 << 20) / (2 * ncls) / 512 * 512);
+    if (several && N > cap_rows)
+      return fail(SBAG_EUNSUPPORTED,
+                  "staged mode over several learner batches needs " +
+                      std::to_string((int64_t)2 * ncls * N) + " bytes of carried class counters (limit 256 MB)");
+    gcnt_rows = std::min(N, cap_rows);
+  }
+  double* d_y = nullptr;
+  TRY(f64_device_labels(const_cast<sbag_dataset*>(ds), ds->lab, N, &d_y));
+  sa.y = d_y;
+  const int64_t tiles = (N + 511) / 512;
+  double* d_out;
+  int32_t *d_noob, *d_gmax = nullptr;
+  uint16_t* d_gcnt = nullptr;
+  uint8_t* d_counts = nullptr;
+  double* d_votes = nullptr;
+  StageStats* d_stats;
+  TRY(ws_typed(c, "pout", (size_t)N, &d_out));
+  TRY(ws_typed(c, "oob_n", (size_t)N, &d_noob));
+  if (mode_agg) TRY(ws_typed(c, "oob_max", (size_t)N, &d_gmax));
+  if (gcnt_rows) TRY(ws_typed(c, "mode_cnt", (size_t)ncls * gcnt_rows, &d_gcnt));
+  if (sp) TRY(ws_typed(c, "counts", (size_t)batch * N, &d_counts));
+  if (!mode_agg) {
+    TRY(ws_typed(c, "stg_se", (size_t)tiles * L, &sa.t_se));
+    TRY(ws_typed(c, "stg_ae", (size_t)tiles * L, &sa.t_ae));
+  }
+  TRY(ws_typed(c, "stg_cov", (size_t)tiles * L, &sa.t_cov));
+  TRY(ws_typed(c, "stg_cor", (size_t)tiles * L, &sa.t_cor));
+  TRY(ws_typed(c, "stg_out", (size_t)L, &d_stats));
+  const DevNode* f_nodes = nullptr;
+  const int64_t* f_off = nullptr;
+  if (tiled) {
+    TRY(upload_plan(c, Pl, pa));
+    pa.codes = ds->d_codes;
+    pa.out = d_out;
+  } else {
+    TRY(upload_forest(c, f, &f_nodes, &f_off));
+    TRY(ws_typed(c, "oob_votes", (size_t)batch * N, &d_votes));
+  }
+  for (int b0 = 0; b0 < L; b0 += batch) {
+    const int b1 = std::min(L, b0 + batch);
+    if (sp) {
+      sbag_sampler_params sb = *sp;
+      sb.learner_begin = sp->learner_begin + b0;
+      sb.learner_end = sp->learner_begin + b1;
+      TRY(run_sampler(c, &sb, poff, N, d_counts, false));
+    }
+    if (tiled) {
+      OobArgs oa{};
+      oa.counts = d_counts;
+      oa.t0 = b0;
+      oa.t1 = b1;
+      oa.first = b0 == 0;
+      oa.last = b1 == L;
+      oa.n_oob = d_noob;
+      oa.gmax = d_gmax;
+      oa.gcnt = d_gcnt;
+      launch_eval_staged(c->stream, pa, oa, sa);
+    } else {  // the batch's per-tree predictions by the global-memory walk, then the staged aggregation
+      launch_predict(c->stream, nullptr, ds->d_codes, ds->code_bytes, ds->d_dict, ds->d_dict_off, N, ds->F,
+                     ds->S, f_nodes, f_off + b0, b1 - b0, kAggVotes, ncls, nullptr, nullptr, d_votes, 8,
+                     nullptr, 0);
+      HIP_TRY(hipGetLastError());
+      launch_staged_agg(c->stream, d_votes, d_counts, b1 - b0, N, agg, ncls, d_out, d_noob, d_gmax, d_gcnt,
+                        gcnt_rows, b0 == 0, b1 == L, b0, sa);
+    }
+    HIP_TRY(hipGetLastError());
+    if (sp && sp->replacement) TRY(sampler_overflow(c));
+  }
+  launch_stage_fold(c->stream, sa, tiles, agg, d_stats);
+  HIP_TRY(hipGetLastError());
+  TRY(d2h(c, reinterpret_cast<StageStats*>(out), (const StageStats*)d_stats, (size_t)L));
+  return SBAG_OK;
+}
+
 }  // extern "C" (host helpers of the raw-prediction entry points)
 
 // ---- per-class raw predictions (sbag_proba.hip).  A call goes through k_proba_tiled when

@@ -348,6 +348,38 @@ void launch_predict_oob(hipStream_t st, const PredictArgs& a, const OobArgs& o);
 void launch_aggregate_oob(hipStream_t st, const double* votes, const uint8_t* counts, int K, int64_t N,
                           int agg, int nclasses, double* out, int32_t* n_oob, int32_t* gmax,
                           uint16_t* gcnt, int64_t gcnt_rows, bool first, bool last);
+// ---- staged evaluation (sbag_staged.hip): per stage l (the forest's first l + 1 trees) the
+// covered rows, the correct ones (mode) and the sums of e * e and |e| (mean) of the
+// out-of-bag (or, without counts, the plain) stage predictions against the labels y.  The
+// order of the two fp64 sums is sbag.h's: rows in tiles of 512 summed by halving, the tile
+// partials [tiles][trees] added in tile order by k_stage_fold.
+constexpr int kStagedMaxGroup = 8;  // stages whose per-thread partials are parked in LDS at once
+struct StagedArgs {
+  const double* y;  // [N] labels
+  int32_t G;        // stages parked per reduction, 1 .. kStagedMaxGroup
+  int32_t trees;    // stages of the call: the stride of a tile's partials
+  double* t_se;     // [tiles][trees] (mean)
+  double* t_ae;     // [tiles][trees] (mean)
+  int32_t* t_cov;   // [tiles][trees]
+  int32_t* t_cor;   // [tiles][trees]
+};
+struct StageStats {  // = sbag_stage_stats
+  int64_t covered, correct;
+  double sum_se, sum_ae;
+};
+// LDS of k_eval_staged past predict_tiled_lds: the parked partials, fp64 [2][G][256] (mean)
+// and the waves' counts int [G][4][2]
+size_t staged_park_lds(int agg, int G);
+// k_eval_staged: k_predict_oob's geometry, plan and carried state (`a`, `o`; o.counts null:
+// no mask, every tree counts for every row); nothing is finalized in a.out
+void launch_eval_staged(hipStream_t st, const PredictArgs& a, const OobArgs& o, const StagedArgs& s);
+// k_staged_agg over a batch's per-tree predictions votes [K][N] (fp64) and bag counts [K][N]
+// (null: no mask), the batch's stages [t0, t0 + K); rows in ranges of gcnt_rows (a multiple
+// of 512, or >= N) for the mode, as launch_aggregate_oob
+void launch_staged_agg(hipStream_t st, const double* votes, const uint8_t* counts, int K, int64_t N,
+                       int agg, int nclasses, double* out, int32_t* n_oob, int32_t* gmax, uint16_t* gcnt,
+                       int64_t gcnt_rows, bool first, bool last, int t0, const StagedArgs& s);
+void launch_stage_fold(hipStream_t st, const StagedArgs& s, int64_t tiles, int agg, StageStats* out);
 // ---- per-class raw predictions (sbag_proba.hip): raw[row][c] over the trees [t0, t1) that
 // count for the row (all of them, or with `counts` those whose bag left the row out), in
 // learner order:

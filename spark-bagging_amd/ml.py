@@ -527,6 +527,37 @@ def oob_metrics(pred, n_oob, y, classification, metricName=None):
     return res
 
 
+_STAGED_METRICS = {False: ("rmse", "mse", "mae"), True: ("accuracy",)}
+
+
+def staged_metrics(stats, num_rows, classification, metricName=None):
+    """The score of every stage of a staged evaluation (`nat.eval_staged`'s records; host
+    arrays, numpy only): {"metric", "values" [L], "coverage" [L], "numRows"}.  Stage l is the
+    ensemble of the first l + 1 learners; coverage = covered / num_rows, and a value is taken
+    over the stage's covered rows only and is NaN where there are none.  Regression: rmse
+    (default) = sqrt(sum_se / covered), mse = sum_se / covered, mae = sum_ae / covered;
+    classification: accuracy = correct / covered.  r2 is refused: its denominator is a
+    two-pass quantity over each stage's own covered rows.  values[-1] agrees with
+    `_BaggingModel.oobScore` to rounding, not to the bit: the device sums the rows in a fixed
+    tile order, oob_metrics with np.mean."""
+    classification = bool(classification)
+    metric = metricName or _STAGED_METRICS[classification][0]
+    if metric not in _STAGED_METRICS[classification]:
+        raise nat.IllegalArgumentException(
+            nat.SBAG_EINVAL, f"metricName given invalid value {metric} "
+                             f"(one of {', '.join(_STAGED_METRICS[classification])})")
+    stats = np.asarray(stats)
+    covered = stats["covered"].astype(np.float64)
+    n = int(num_rows)
+    top = {"accuracy": stats["correct"].astype(np.float64), "mae": stats["sum_ae"]}.get(metric, stats["sum_se"])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        values = np.where(covered > 0, top / covered, np.nan)
+        if metric == "rmse":
+            values = np.sqrt(values)
+        coverage = covered / n if n else np.zeros(len(stats))
+    return {"metric": metric, "values": values.astype(np.float64), "coverage": coverage, "numRows": n}
+
+
 def oob_permutation_importance(base_pred, perm_pred, n_oob, y, classification, metricName=None):
     """Permutation importances from out-of-bag predictions (host arrays, numpy only):
     {"metric", "baseline", "permuted" [K], "importance" [K]}.  baseline and permuted[k] are
@@ -736,6 +767,41 @@ class _BaggingModel(_BaggingParams):
         else:
             y = dataset.label if isinstance(dataset, Frame) else dataset[1]
         return oob_metrics(pred, n_oob, y, self._agg == nat.AGG_MODE, metricName)
+
+    def oobScoreCurve(self, dataset, metricName=None, partition_offsets=None):
+        """The out-of-bag score as a function of the number of learners, in one pass on the
+        device (staged_metrics of nat.eval_staged): {"metric", "values" [numBaseModels],
+        "coverage" [numBaseModels], "numRows"}, entry l the out-of-bag score of the first
+        l + 1 learners.  Inputs as oobScore's; the last entry agrees with oobScore to rounding."""
+        (lb, le), ds, part, own = self._oob_dataset(dataset, partition_offsets)
+        try:
+            stats = nat.eval_staged(ds.ctx, self.native_forest(), ds, agg=self._agg,
+                                    replacement=self.get("replacement"), sample_ratio=self.get("sampleRatio"),
+                                    seed=self.get("seed"), learner_begin=lb, learner_end=le,
+                                    partition_offsets=part)
+            n = ds.shape[0]
+        finally:
+            if own:
+                ds.free()
+        return staged_metrics(stats, n, self._agg == nat.AGG_MODE, metricName)
+
+    def evaluateEachIteration(self, dataset, metricName=None):
+        """The score of the first l + 1 learners on `dataset` (a Frame, (X, y) or a
+        DeviceDataset with labels) for every l, no learner masked: the held-out curve
+        (GBTRegressionModel.evaluateEachIteration), in the form of oobScoreCurve."""
+        own = not isinstance(dataset, nat.DeviceDataset)
+        if own:
+            frame = dataset if isinstance(dataset, Frame) else Frame(dataset[0], dataset[1])
+            ds = frame.device_dataset(nat.default_context(0))
+        else:
+            ds = dataset
+        try:
+            stats = nat.eval_staged(ds.ctx, self.native_forest(), ds, agg=self._agg)
+            n = ds.shape[0]
+        finally:
+            if own:
+                ds.free()
+        return staged_metrics(stats, n, self._agg == nat.AGG_MODE, metricName)
 
     def predict(self, features):
         """Single-vector predict (BaggingRegressor.scala:248-256 / BaggingClassifier.scala:248-257)."""
