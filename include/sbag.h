@@ -481,6 +481,47 @@ int sbag_predict_weighted(sbag_ctx* ctx, const sbag_forest* f, const double* X, 
 int sbag_predict_weighted_dataset(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* ds,
                                   int32_t kind, const double* weights, int32_t num_weights,
                                   int32_t num_cols, double* out);
+/* ---- per-row quantiles across the trees of a regression forest: the spread of the ensemble
+ * (prediction intervals; out of bag, their calibration).  out is host fp64
+ * [num_rows x num_probs], row-major; probs is host [num_probs].
+ *   Values.  For row r take the predictions of the trees concerned, -0.0 read as +0.0, sorted
+ *            ascending: v[0, n).  sbag_predict_quantiles(_dataset): every tree, n = the tree
+ *            count.  sbag_predict_oob_quantiles: the learners i with counts[i][r] == 0 of the
+ *            sampler's bags (sbag_sample), n = n_oob[r], byte for byte sbag_predict_oob's
+ *            n_oob_out.
+ *   Index.   For probability p: h = (double)(n - 1) * p (one rounded product), lo = floor(h),
+ *            g = h - lo.
+ *   Result.  out = v[lo] when g == 0, else v[lo] + g * (v[lo + 1] - v[lo]), the subtraction,
+ *            the product and the sum each rounded to fp64 on their own (no FMA).  out = NaN
+ *            where n == 0.  This is NumPy's `linear` quantile up to the rounding of the
+ *            interpolation, and exactly an order statistic where g == 0.
+ * num_rows == 0 is SBAG_OK.
+ * SBAG_EINVAL (nothing written, the context stays usable): a null argument (n_oob_out may be
+ * NULL), a gini forest, num_probs outside [1, 64], a probability that is NaN or outside
+ * [0, 1], a leaf that predicts NaN (hand-built forests only), and the argument errors of
+ * sbag_predict / sbag_predict_dataset / sbag_predict_oob (a subspace past the features, ds on
+ * another device, a sampler range that is not the forest's, bad partition offsets).
+ * SBAG_EUNSUPPORTED: more than 1024 trees; for the out-of-bag call a forest whose bag counts
+ * (trees x num_rows bytes) do not fit one learner batch of sbag_predict_oob (or
+ * SBAG_OOB_BATCH_LEARNERS below the tree count): a row's quantile needs all its learners at
+ * once.
+ * A row's values are carried as ranks in the forest's dictionary of sorted distinct leaf
+ * values.  u8 / u16 codes, at most 65 535 distinct leaf values, and a row tile (512, 256, 128
+ * or 64 rows) whose rows, u16 rank matrix and a forest chunk fit the LDS go through one fused
+ * pass that walks the trees and sorts each row's ranks in a wave (host rows are binned against
+ * the forest's thresholds first, in row batches as in sbag_predict); u32 codes, more distinct
+ * values, larger trees, a feature of host rows with more than 65 535 thresholds, and every
+ * call under SBAG_QUANT_FORCE_FALLBACK=1 (read on every call) walk global memory, one thread
+ * per row, and sort u32 ranks in a second kernel: the same bits.                          */
+int sbag_predict_quantiles(sbag_ctx* ctx, const sbag_forest* f, const double* X, int64_t num_rows,
+                           int32_t num_features, const double* probs /* host [num_probs] */,
+                           int32_t num_probs, double* out /* host [num_rows x num_probs] */);
+int sbag_predict_quantiles_dataset(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* ds,
+                                   const double* probs, int32_t num_probs, double* out);
+int sbag_predict_oob_quantiles(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* ds,
+                               const sbag_sampler_params* sampler, const int64_t* partition_offsets,
+                               int32_t num_partitions, const double* probs, int32_t num_probs,
+                               double* out, int32_t* n_oob_out /* host [num_rows] or NULL */);
 /* ---- Stacking: the level-1 dataset and the two-level transform -----------------------------
  * StackingRegressor.train (ml/regression/StackingRegressor.scala:163-171) and
  * StackingClassifier.train (ml/classification/StackingClassifier.scala:164-172) map every

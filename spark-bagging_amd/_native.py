@@ -37,6 +37,7 @@ EXPORTED = [
     "sbag_sample_boosted", "sbag_sample_boosted_stats", "sbag_fit_bag",
     "sbag_dataset_create_stacked", "sbag_predict_stacked", "sbag_predict_stacked_dataset",
     "sbag_predict_weighted", "sbag_predict_weighted_dataset", "sbag_eval_staged",
+    "sbag_predict_quantiles", "sbag_predict_quantiles_dataset", "sbag_predict_oob_quantiles",
 ]
 
 
@@ -177,6 +178,9 @@ def lib():
             "sbag_predict_oob_raw": [P, P, P, ctypes.POINTER(SamplerParams), P, i32, i32, i32, P, P],
             "sbag_predict_weighted": [P, P, P, i64, i32, i32, P, i32, i32, P],
             "sbag_predict_weighted_dataset": [P, P, P, i32, P, i32, i32, P],
+            "sbag_predict_quantiles": [P, P, P, i64, i32, P, i32, P],
+            "sbag_predict_quantiles_dataset": [P, P, P, P, i32, P],
+            "sbag_predict_oob_quantiles": [P, P, P, ctypes.POINTER(SamplerParams), P, i32, P, i32, P, P],
             "sbag_forest_timing": [P, ctypes.POINTER(Timing)],
             "sbag_predict": [P, P, P, i64, i32, i32, P, P],
             "sbag_predict_dataset": [P, P, P, i32, P],
@@ -752,6 +756,47 @@ def predict_weighted_dataset(ctx, forest, dataset, kind, weights, num_cols=1):
     check(lib().sbag_predict_weighted_dataset(ctx.handle, forest.handle, dataset.handle, kind, ptr(w),
                                               len(w), int(num_cols), ptr(out)))
     return out
+
+
+def predict_quantiles(ctx, forest, X, probs):
+    """Per-row quantiles across the trees of host rows (sbag_predict_quantiles): fp64
+    [N, len(probs)], sbag.h's rule (NumPy's `linear` method, each step rounded on its own)."""
+    X = np.ascontiguousarray(X, np.float64)
+    p = np.ascontiguousarray(probs, np.float64).reshape(-1)
+    out = np.zeros((X.shape[0], len(p)), np.float64)
+    check(lib().sbag_predict_quantiles(ctx.handle, forest.handle, ptr(X), X.shape[0], X.shape[1], ptr(p),
+                                       len(p), ptr(out)))
+    return out
+
+
+def predict_quantiles_dataset(ctx, forest, dataset, probs):
+    """predict_quantiles over a device dataset (sbag_predict_quantiles_dataset): no feature and
+    no per-tree prediction leaves the device."""
+    p = np.ascontiguousarray(probs, np.float64).reshape(-1)
+    out = np.zeros((dataset.shape[0], len(p)), np.float64)
+    check(lib().sbag_predict_quantiles_dataset(ctx.handle, forest.handle, dataset.handle, ptr(p), len(p),
+                                               ptr(out)))
+    return out
+
+
+def predict_oob_quantiles(ctx, forest, dataset, probs, *, replacement, sample_ratio, seed, learner_begin,
+                          learner_end, partition_offsets=None):
+    """Out-of-bag quantiles (sbag_predict_oob_quantiles), the sampler arguments as predict_oob's:
+    (q fp64 [N, len(probs)] over the learners that left the row out, NaN where there is none;
+    n_oob int32 [N], predict_oob's)."""
+    sp = SamplerParams(int(replacement), 0, float(sample_ratio), int(seed), learner_begin, learner_end)
+    off = None
+    P = 1
+    if partition_offsets is not None:
+        off = np.ascontiguousarray(partition_offsets, np.int64)
+        P = len(off) - 1
+    p = np.ascontiguousarray(probs, np.float64).reshape(-1)
+    n = dataset.shape[0]
+    out = np.zeros((n, len(p)), np.float64)
+    n_oob = np.zeros(n, np.int32)
+    check(lib().sbag_predict_oob_quantiles(ctx.handle, forest.handle, dataset.handle, ctypes.byref(sp), ptr(off),
+                                           P, ptr(p), len(p), ptr(out), ptr(n_oob)))
+    return out, n_oob
 
 
 def predict_stacked(ctx, base, stack, X_or_dataset):

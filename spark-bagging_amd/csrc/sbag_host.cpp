@@ -35,6 +35,7 @@
 #include "sbag_fastmath.h"
 #include "sbag_internal.h"
 #include "sbag_mfma_plan.h"
+#include "sbag_spread_plan.h"
 #include "sbag_stack_plan.h"
 
 using namespace sbag;
@@ -5075,12 +5076,14 @@ template <typename TC>
 static bool plan_tiled(const sbag_forest* f, PredictArgs& pa, int F, TC tc_of, TiledPlan& P,
                        size_t extra_fixed = 0 /* LDS the kernel holds besides predict_tiled_lds */,
                        int leaf_w = 0 /* > 0: a leaf's payload is its leaf_w class fractions
-                                         (leaf_fractions), its node's index the leaf's ordinal */) {
+                                         (leaf_fractions), its node's index the leaf's ordinal */,
+                       int tile_rows = kSpreadTileRows /* rows the kernel stages, <= 512 */) {
   const int L = (int)f->trees.size();
   pa.L = L;
   pa.nclasses = std::max(f->nclasses, 1);
   pa.chunk_bytes = 0;
-  const size_t fixed = predict_tiled_lds(pa) + extra_fixed;
+  const size_t fixed = predict_tiled_lds(pa) + extra_fixed -
+                       (size_t)(kSpreadTileRows - tile_rows) * ((size_t)pa.S * pa.code_bytes + 4);
   const size_t lds_cap = 160 * 1024 - 512;
   if (F >= 32768 || fixed + 4096 > lds_cap) return false;
   const int budget = (int)std::min<size_t>(64 * 1024, lds_cap - fixed) & ~15;
@@ -5689,6 +5692,281 @@ static int raw_prepare(sbag_ctx* c, const sbag_forest* f, int kind, int code_byt
   if (kind == SBAG_RAW_LEAF) TRY(upload_fractions(c, f, &R.frac, &R.leaf_off));
   return SBAG_OK;
 }
+
+// ---- per-row quantiles across the trees (sbag_spread.hip).  A call goes through
+// k_quant_tiled when the forest's dictionary has at most 65 535 values, spread_tile_rows finds a
+// row tile and plan_tiled holds the forest beside the tile's rank matrix (u8 / u16 codes, every
+// tree within the chunk), and SBAG_QUANT_FORCE_FALLBACK is not set (read on every call); else
+// through k_quant_walk + k_quant_select in row batches of at most 256 MB of u32 keys.
+static int check_quantiles(const sbag_forest* f, const double* probs, int32_t num_probs) {
+  if (f->impurity == SBAG_IMPURITY_GINI) return fail(SBAG_EINVAL, "quantiles need a regression forest");
+  if (num_probs < 1 || num_probs > kSpreadMaxProbs)
+    return fail(SBAG_EINVAL, "num_probs must be in [1, " + std::to_string(kSpreadMaxProbs) + "]");
+  for (int i = 0; i < num_probs; i++)
+    if (!(probs[i] >= 0.0 && probs[i] <= 1.0))
+      return fail(SBAG_EINVAL, "probability " + std::to_string(i) + " is outside [0, 1]");
+  for (const HTree& t : f->trees)
+    for (const sbag_node& n : t.nodes)
+      if (n.left < 0 && n.prediction != n.prediction) return fail(SBAG_EINVAL, "a leaf predicts NaN");
+  const int L = (int)f->trees.size();
+  if (L > kSpreadMaxTrees)
+    return fail(SBAG_EUNSUPPORTED, "quantiles over " + std::to_string(L) + " trees (limit " +
+                                       std::to_string(kSpreadMaxTrees) + ")");
+  return SBAG_OK;
+}
+
+struct QuantRun {
+  bool tiled = false;
+  PredictArgs pa{};                // tiled: the uploaded plan (codes / N set per launch)
+  const DevNode* nodes = nullptr;  // general path
+  const int64_t* off = nullptr;
+  const uint32_t* leaf_rank = nullptr;  // general path: the rank of every leaf, a tree's leaves
+  const int64_t* leaf_off = nullptr;    // in node order from leaf_off[t] (DevNode.pad)
+  uint32_t* keys = nullptr;             // general path: [L][batch]
+  int64_t batch = 0;
+  QuantArgs q{};
+};
+
+// the plan of a quantile pass over codes of `code_bytes` at row stride S (tc_of: a threshold in
+// code space, as plan_tiled's), uploaded with the dictionary and the probabilities; may_tile
+// false: the general path, its key workspace sized for N rows
+template <typename TC>
+static int quant_prepare(sbag_ctx* c, const sbag_forest* f, const double* probs, int nq, int code_bytes,
+                         int S, int F, bool may_tile, int64_t N, TC tc_of, QuantRun& R) {
+  const int L = (int)f->trees.size();
+  const char* ffb = getenv("SBAG_QUANT_FORCE_FALLBACK");
+  if (ffb && atoi(ffb) != 0) may_tile = false;
+  std::vector<double> leaves, dict;
+  for (const HTree& t : f->trees)
+    for (const sbag_node& n : t.nodes)
+      if (n.left < 0) leaves.push_back(n.prediction);
+  if (!spread_dictionary(leaves, dict)) return fail(SBAG_EINVAL, "a leaf predicts NaN");
+  double *d_dict, *d_probs;
+  TRY(ws_typed(c, "qn_dict", std::max<size_t>(dict.size(), 1), &d_dict));
+  TRY(ws_typed(c, "qn_probs", (size_t)nq, &d_probs));
+  TRY(h2d(c, d_dict, dict.data(), dict.size()));
+  TRY(h2d(c, d_probs, probs, (size_t)nq));
+  R.q.dict = d_dict;
+  R.q.probs = d_probs;
+  R.q.Q = nq;
+  R.pa.code_bytes = code_bytes;
+  R.pa.S = S;
+  R.pa.agg = kAggMean;  // predict_tiled_lds: the row tile and the chunk; the rank matrix is extra
+  const int Rt = may_tile && dict.size() <= 65535 ? spread_tile_rows(S * code_bytes + 4, L) : 0;
+  TiledPlan P;
+  R.tiled = Rt > 0 && plan_tiled(f, R.pa, F, tc_of, P, spread_matrix_lds(L, Rt), 0, Rt);
+  if (R.tiled) {
+    R.q.R = Rt;
+    for (int t = 0; t < L; t++) {  // a leaf node carries the rank of its value
+      const int64_t n1 = t + 1 < L ? P.tn[t + 1] : (int64_t)P.pn.size();
+      for (int64_t k = P.tn[t]; k < n1; k++)
+        if (P.pn[k].a & 0x80000000u)
+          P.pn[k].a = 0x80000000u | spread_rank(dict, P.lv[P.tl[t] + (P.pn[k].a & 0x7fffffffu)]);
+    }
+    return upload_plan(c, P, R.pa);
+  }
+  TRY(upload_forest(c, f, &R.nodes, &R.off));
+  std::vector<uint32_t> lr;
+  std::vector<int64_t> lo;
+  lr.reserve(leaves.size());
+  for (const HTree& t : f->trees) {
+    lo.push_back((int64_t)lr.size());
+    for (const sbag_node& n : t.nodes)
+      if (n.left < 0) lr.push_back(spread_rank(dict, n.prediction));
+  }
+  uint32_t* d_lr;
+  int64_t* d_lo;
+  TRY(ws_typed(c, "qn_lrank", std::max<size_t>(lr.size(), 1), &d_lr));
+  TRY(ws_typed(c, "qn_loff", std::max<size_t>(lo.size(), 1), &d_lo));
+  TRY(h2d(c, d_lr, lr.data(), lr.size()));
+  TRY(h2d(c, d_lo, lo.data(), lo.size()));
+  R.leaf_rank = d_lr;
+  R.leaf_off = d_lo;
+  R.batch = std::max<int64_t>(1, std::min<int64_t>(N, ((int64_t)256 << 20) / (4 * (int64_t)std::max(L, 1))));
+  TRY(ws_typed(c, "qn_keys", (size_t)R.batch * std::max(L, 1), &R.keys));
+  return SBAG_OK;
+}
+
+// the general path over N rows (X fp64 rows on the device, or a dataset's codes), R.q.out /
+// R.q.n_oob / R.q.counts (row stride N) set for row 0
+static int quant_general(sbag_ctx* c, const QuantRun& R, const double* d_X, const sbag_dataset* ds, int64_t N,
+                         int F, int L) {
+  for (int64_t r0 = 0; r0 < N; r0 += R.batch) {
+    const int64_t n = std::min(R.batch, N - r0);
+    QuantArgs q = R.q;
+    q.out = R.q.out + r0 * q.Q;
+    if (q.n_oob) q.n_oob += r0;
+    const uint8_t* cnt = q.counts ? q.counts + r0 : nullptr;
+    if (d_X)
+      launch_quant_walk(c->stream, d_X + r0 * F, nullptr, 1, nullptr, nullptr, n, F, F, R.nodes, R.off,
+                        R.leaf_rank, R.leaf_off, L, cnt, N, R.keys);
+    else
+      launch_quant_walk(c->stream, nullptr, (const unsigned char*)ds->d_codes + (size_t)r0 * ds->S * ds->code_bytes,
+                        ds->code_bytes, ds->d_dict, ds->d_dict_off, n, ds->F, ds->S, R.nodes, R.off,
+                        R.leaf_rank, R.leaf_off, L, cnt, N, R.keys);
+    HIP_TRY(hipGetLastError());
+    launch_quant_select(c->stream, R.keys, n, L, q);
+    HIP_TRY(hipGetLastError());
+  }
+  return SBAG_OK;
+}
+
+extern "C" {
+
+int sbag_predict_quantiles(sbag_ctx* c, const sbag_forest* f, const double* X, int64_t N, int32_t F,
+                           const double* probs, int32_t num_probs, double* out) {
+  if (!c || !f || !X || !probs || !out || N < 0 || F <= 0) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(check_quantiles(f, probs, num_probs));
+  for (const HTree& t : f->trees)
+    for (int32_t g : t.sub)
+      if (g >= F) return fail(SBAG_EINVAL, "feature vector shorter than a subspace index");
+  HIP_TRY(hipSetDevice(c->device));
+  const int L = (int)f->trees.size();
+  // rows are binned on the device against the forest's own thresholds, as in sbag_predict
+  std::vector<std::vector<double>> T(F);
+  for (const HTree& t : f->trees)
+    for (const sbag_node& n : t.nodes)
+      if (n.left >= 0) T[t.sub[n.feature]].push_back(n.threshold);
+  std::vector<int64_t> toff(F + 1, 0);
+  size_t max_thr = 0;
+  for (int g = 0; g < F; g++) {
+    std::sort(T[g].begin(), T[g].end());
+    T[g].erase(std::unique(T[g].begin(), T[g].end()), T[g].end());
+    toff[g + 1] = toff[g] + (int64_t)T[g].size();
+    max_thr = std::max(max_thr, T[g].size());
+  }
+  const int32_t Sq = (F + 15) / 16 * 16;
+  QuantRun R;
+  TRY(quant_prepare(c, f, probs, num_probs, 2, Sq, F, max_thr <= 65535, N, [&](int g, double thr) {
+    return (int64_t)(std::lower_bound(T[g].begin(), T[g].end(), thr) - T[g].begin());
+  }, R));
+  if (N == 0) return SBAG_OK;
+  double* d_out;
+  TRY(ws_typed(c, "pqout", (size_t)N * num_probs, &d_out));
+  double* d_X;
+  if (R.tiled) {
+    std::vector<double> tv((size_t)std::max<int64_t>(toff[F], 1));
+    for (int g = 0; g < F; g++) std::copy(T[g].begin(), T[g].end(), tv.begin() + toff[g]);
+    double* d_T;
+    int64_t* d_toff;
+    TRY(ws_typed(c, "pq_thr", tv.size(), &d_T));
+    TRY(ws_typed(c, "pq_off", toff.size(), &d_toff));
+    TRY(h2d(c, d_T, tv.data(), tv.size()));
+    TRY(h2d(c, d_toff, toff.data(), toff.size()));
+    int64_t batch = std::max<int64_t>(1, std::min<int64_t>(N, ((int64_t)2 << 30) / (8 * (int64_t)F)));
+    if (const char* e = getenv("SBAG_PREDICT_BATCH_ROWS")) batch = std::max<int64_t>(1, std::min<int64_t>(batch, atoll(e)));
+    uint16_t* d_codes;
+    TRY(ws_typed(c, "pX", (size_t)batch * F, &d_X));
+    TRY(ws_typed(c, "pq_codes", (size_t)batch * Sq, &d_codes));
+    for (int64_t r0 = 0; r0 < N; r0 += batch) {
+      const int64_t n = std::min(batch, N - r0);
+      HIP_TRY(hipMemcpyAsync(d_X, X + r0 * F, (size_t)n * F * 8, hipMemcpyHostToDevice, c->stream));
+      launch_quantize(c->stream, d_X, n, F, d_T, d_toff, d_codes, Sq);
+      R.pa.codes = d_codes;
+      R.pa.N = n;
+      R.q.out = d_out + r0 * num_probs;
+      launch_quant_tiled(c->stream, R.pa, R.q);
+      HIP_TRY(hipGetLastError());
+    }
+  } else {
+    TRY(ws_typed(c, "pX", (size_t)N * F, &d_X));
+    TRY(h2d(c, d_X, X, (size_t)N * F));
+    R.q.out = d_out;
+    TRY(quant_general(c, R, d_X, nullptr, N, F, L));
+  }
+  TRY(d2h(c, out, d_out, (size_t)N * num_probs));
+  return SBAG_OK;
+}
+
+// the checks a dataset call shares with its siblings
+static int check_quant_dataset(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds) {
+  for (const HTree& t : f->trees)
+    for (int32_t g : t.sub)
+      if (g >= ds->F) return fail(SBAG_EINVAL, "dataset has fewer features than the model");
+  if (ds->ctx->device != c->device)
+    return fail(SBAG_EINVAL, "dataset lives on device " + std::to_string(ds->ctx->device) +
+                                 ", the context on device " + std::to_string(c->device));
+  return SBAG_OK;
+}
+
+// a resident dataset through either path; R.q.counts / R.q.n_oob set by the caller
+static int quant_dataset(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds, const double* probs,
+                         int num_probs, QuantRun& R, double* out) {
+  // TreePoint's `value <= threshold` in the dataset's code space (dict sorted ascending)
+  TRY(quant_prepare(c, f, probs, num_probs, ds->code_bytes, ds->S, ds->F, ds->code_bytes != 4, ds->N,
+                    [&](int g, double thr) {
+                      const std::vector<double>& d = ds->dict[g];
+                      return (int64_t)(std::upper_bound(d.begin(), d.end(), thr) - d.begin()) - 1;
+                    }, R));
+  if (ds->N == 0) return SBAG_OK;
+  double* d_out;
+  TRY(ws_typed(c, "pqout", (size_t)ds->N * num_probs, &d_out));
+  R.q.out = d_out;
+  if (R.tiled) {
+    R.pa.codes = ds->d_codes;
+    R.pa.N = ds->N;
+    launch_quant_tiled(c->stream, R.pa, R.q);
+    HIP_TRY(hipGetLastError());
+  } else {
+    TRY(quant_general(c, R, nullptr, ds, ds->N, ds->F, (int)f->trees.size()));
+  }
+  TRY(d2h(c, out, d_out, (size_t)ds->N * num_probs));
+  return SBAG_OK;
+}
+
+int sbag_predict_quantiles_dataset(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds,
+                                   const double* probs, int32_t num_probs, double* out) {
+  if (!c || !f || !ds || !probs || !out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(check_quantiles(f, probs, num_probs));
+  TRY(check_quant_dataset(c, f, ds));
+  HIP_TRY(hipSetDevice(c->device));
+  QuantRun R;
+  return quant_dataset(c, f, ds, probs, num_probs, R, out);
+}
+
+int sbag_predict_oob_quantiles(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds,
+                               const sbag_sampler_params* sp, const int64_t* partition_offsets, int32_t P,
+                               const double* probs, int32_t num_probs, double* out, int32_t* n_oob_out) {
+  if (!c || !f || !ds || !sp || !probs || !out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(check_sampler(sp));
+  TRY(check_quantiles(f, probs, num_probs));
+  const int L = (int)f->trees.size();
+  if (sp->learner_end - sp->learner_begin != L)
+    return fail(SBAG_EINVAL, "the sampler's learner range holds " +
+                                 std::to_string(sp->learner_end - sp->learner_begin) +
+                                 " learners, the forest " + std::to_string(L) + " trees");
+  const int64_t N = ds->N;
+  if (partition_offsets && P >= 1 && partition_offsets[P] != N)
+    return fail(SBAG_EINVAL, "partition_offsets must end at the dataset's row count");
+  std::vector<int64_t> poff;
+  TRY(check_partitions(P, partition_offsets, N, poff));
+  TRY(check_quant_dataset(c, f, ds));
+  HIP_TRY(hipSetDevice(c->device));
+  QuantRun R;
+  if (N > 0) {
+    // a row's quantile needs all its learners at once: the counts of every learner, one batch
+    int batch = (int)std::max(1.0, std::min((double)L, std::floor(bins_budget(c) / (double)N)));
+    if (const char* e = getenv("SBAG_OOB_BATCH_LEARNERS")) batch = std::max(1, std::min(L, atoi(e)));
+    if (batch < L)
+      return fail(SBAG_EUNSUPPORTED, "out-of-bag quantiles need the bag counts of all " + std::to_string(L) +
+                                         " learners at once; " + std::to_string(batch) + " fit a batch");
+    uint8_t* d_counts;
+    int32_t* d_noob;
+    TRY(ws_typed(c, "counts", (size_t)L * N, &d_counts));
+    TRY(ws_typed(c, "oob_n", (size_t)N, &d_noob));
+    TRY(run_sampler(c, sp, poff, N, d_counts));
+    R.q.counts = d_counts;
+    R.q.n_oob = d_noob;
+  }
+  TRY(quant_dataset(c, f, ds, probs, num_probs, R, out));
+  if (n_oob_out && N > 0) TRY(d2h(c, n_oob_out, R.q.n_oob, (size_t)N));
+  return SBAG_OK;
+}
+
+}  // extern "C"
 
 // ---- weighted sums over the trees (sbag_wpred.hip).  A call goes through k_wpred_tiled when
 // plan_tiled holds the forest beside the accumulators (u8 / u16 codes, every tree within the

@@ -433,6 +433,32 @@ void launch_wpred_tiled(hipStream_t st, const PredictArgs& a, const WpredArgs& q
 void launch_wpred_walk(hipStream_t st, const double* X, const void* codes, int code_bytes,
                        const double* dict, const int64_t* dict_off, int64_t N, int32_t F, int32_t S,
                        const DevNode* nodes, const int64_t* tree_off, int L, const WpredArgs& q);
+// ---- per-row quantiles across the trees (sbag_spread.hip): a row's predictions as ranks in
+// the forest's dictionary of sorted distinct leaf values, sorted by one wave, the ranks a
+// probability lands between turned back into values (sbag.h's rule).  The all-ones key (u16
+// on the tiled path, u32 on the general one) is "in bag / padding" and sorts last.
+struct QuantArgs {
+  const double* dict;     // [D] the dictionary, on the device
+  const double* probs;    // [Q] on the device
+  int32_t Q;              // probabilities, 1 .. 64
+  int32_t R;              // k_quant_tiled: rows of a tile (sbag_spread_plan.h)
+  const uint8_t* counts;  // [L][N] bag multiplicities of all the trees, or null: every tree counts
+  double* out;            // [N][Q], row-major
+  int32_t* n_oob;         // [N] trees counted per row (with counts), or null
+};
+// k_quant_tiled: k_wpred_tiled's geometry at q.R rows a tile over a plan whose leaf nodes hold
+// 0x80000000 | rank (no leaf values); LDS = q.R rows + a.chunk_bytes + spread_matrix_lds
+void launch_quant_tiled(hipStream_t st, const PredictArgs& a, const QuantArgs& q);
+// k_quant_walk: one thread per row of a batch of n over DevNodes in global memory (X fp64 rows,
+// or codes + dictionaries as launch_predict); keys[l][row] = leaf_rank[leaf_off[l] + the
+// leaf's DevNode.pad], or the last key where counts[l * cstride + row] != 0
+void launch_quant_walk(hipStream_t st, const double* X, const void* codes, int code_bytes,
+                       const double* dict, const int64_t* dict_off, int64_t n, int32_t F, int32_t S,
+                       const DevNode* nodes, const int64_t* tree_off, const uint32_t* leaf_rank,
+                       const int64_t* leaf_off, int L, const uint8_t* counts, int64_t cstride,
+                       uint32_t* keys);
+// k_quant_select: a wave per row over keys [L][n]; q.out / q.n_oob are the batch's first row's
+void launch_quant_select(hipStream_t st, const uint32_t* keys, int64_t n, int L, const QuantArgs& q);
 // ---- out-of-bag predictions under permuted features (sbag_oobperm.hip): slot k of a
 // feature batch is sbag_predict_oob with feature feat[k] of row r taken from row src[k][r].
 // Between learner batches a slot's state lives in global memory as the baseline's does:

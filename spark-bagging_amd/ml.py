@@ -876,6 +876,49 @@ class BaggingRegressionModel(_BaggingModel):
     _defaults = dict(_BaggingParams._defaults,
                      seed=java_string_hash("org.apache.spark.ml.regression.BaggingRegressionModel"))
 
+    def predictQuantiles(self, dataset, probabilities, device=0):
+        """Per-row quantiles of the trees' predictions, fp64 [N, len(probabilities)]: NumPy's
+        `linear` method over the ensemble's values of a row (sbag.h states the rounding),
+        sorted and selected on the device in the pass that walks the trees.  `dataset` as in
+        transform; a DeviceDataset stays resident."""
+        forest = self.native_forest()
+        if isinstance(dataset, nat.DeviceDataset):
+            return nat.predict_quantiles_dataset(dataset.ctx, forest, dataset, probabilities)
+        ctx = nat.default_context(device)
+        X = dataset.features if isinstance(dataset, Frame) else dataset
+        if is_sparse(X):
+            ds = nat.DeviceDataset.from_csr(X, np.zeros(X.shape[0]), ctx)
+            try:
+                return nat.predict_quantiles_dataset(ctx, forest, ds, probabilities)
+            finally:
+                ds.free()
+        X = np.asarray(X, np.float64)
+        if X.ndim == 1:
+            X = X[None, :]
+        return nat.predict_quantiles(ctx, forest, X, probabilities)
+
+    def predictInterval(self, dataset, coverage=0.9, device=0):
+        """(lower, upper): the ensemble's quantiles at (1 - coverage) / 2 and (1 + coverage) / 2."""
+        coverage = float(coverage)
+        if not 0.0 <= coverage <= 1.0:
+            raise nat.IllegalArgumentException(nat.SBAG_EINVAL, f"coverage given invalid value {coverage}")
+        q = self.predictQuantiles(dataset, [(1.0 - coverage) / 2, (1.0 + coverage) / 2], device)
+        return q[:, 0].copy(), q[:, 1].copy()
+
+    def oobQuantiles(self, dataset, probabilities, partition_offsets=None):
+        """Out-of-bag quantiles on the training data: (q [N, len(probabilities)], n_oob).  Row
+        r's quantiles are taken over the learners whose bag did not draw it (NaN where there is
+        none); `dataset` and `partition_offsets` as in oobPredictions."""
+        (lb, le), ds, part, own = self._oob_dataset(dataset, partition_offsets)
+        try:
+            return nat.predict_oob_quantiles(ds.ctx, self.native_forest(), ds, probabilities,
+                                             replacement=self.get("replacement"),
+                                             sample_ratio=self.get("sampleRatio"), seed=self.get("seed"),
+                                             learner_begin=lb, learner_end=le, partition_offsets=part)
+        finally:
+            if own:
+                ds.free()
+
 
 _VOTING = {"soft": nat.RAW_LEAF, "hard": nat.RAW_VOTES}
 
@@ -924,6 +967,12 @@ class BaggingClassificationModel(_BaggingModel):
     _estimator_seed_default = java_string_hash("org.apache.spark.ml.classification.BaggingClassifier")
     _defaults = dict(_BaggingParams._defaults,
                      seed=java_string_hash("org.apache.spark.ml.classification.BaggingClassificationModel"))
+
+    def _no_spread(self, *_a, **_k):
+        raise nat.IllegalArgumentException(
+            nat.SBAG_EINVAL, f"{type(self).__name__} has no quantiles of its votes (a regression model does)")
+
+    predictQuantiles = predictInterval = oobQuantiles = _no_spread
 
     @property
     def numClasses(self):
