@@ -522,6 +522,65 @@ int sbag_predict_oob_quantiles(sbag_ctx* ctx, const sbag_forest* f, const sbag_d
                                const sbag_sampler_params* sampler, const int64_t* partition_offsets,
                                int32_t num_partitions, const double* probs, int32_t num_probs,
                                double* out, int32_t* n_oob_out /* host [num_rows] or NULL */);
+/* ---- partial dependence of the ensemble on one feature (randomForest's partialPlot, sklearn's
+ * partial_dependence): how the prediction, averaged over the rows, moves when feature `feature`
+ * (a global index) of every row is set to each of the grid's values in turn.
+ * For a forest of L trees, N rows and a grid[0 .. G), finite and strictly ascending,
+ * 1 <= G <= 256, define cnt[t][l][g] as the number of rows r for which tree t reaches its leaf
+ * l when the tree reads grid[g] in place of the feature and row r's own value for every other
+ * feature.  l counts the tree's leaves in pre-order (the order of their node ids).  A node
+ * that tests the feature sends grid[g] left iff grid[g] <= threshold (Split.shouldGoLeft),
+ * compared in fp64 against the node's own threshold, not through a dataset's dictionary: a grid
+ * value need not be a value of the data.  A tree whose subspace lacks the feature is unaffected
+ * by the substitution.  The counts are integers: any accumulation order gives the same value.
+ * From the counts, in an order that is part of the interface:
+ *   SBAG_PD_MEAN   (a forest of any impurity)
+ *                  tree_pd[t][g] = s / (double)N, where s starts at 0.0 and adds
+ *                  (double)cnt[t][l][g] * value_l for l in pre-order, each product rounded on its
+ *                  own: no FMA, no reassociation.
+ *                  weights == NULL: pd[g] = (in-order sum over t of tree_pd[t][g]) / (double)L,
+ *                  the bagging regressor's mean (BaggingRegressor.scala:248-256).
+ *                  weights != NULL: pd[g] = in-order sum over t of (tree_pd[t][g] * weights[t]),
+ *                  the product rounded first: GBMRegressionModel's BLAS.dot
+ *                  (GBMRegressor.scala:511-516); the caller adds `const` or divides by
+ *                  sumWeights.
+ *   SBAG_PD_VOTES  (a gini forest, num_classes >= sbag_forest_num_classes; weights and
+ *                  per_tree_out NULL)
+ *                  votes[g][c] = the integer sum over t and over the leaves l that predict class
+ *                  c of cnt[t][l][g]; pd[g][c] = (double)votes[g][c] / ((double)N * (double)L).
+ *                  Columns past the forest's class count are 0.0.
+ * out is host [G] (MEAN) or [G x num_classes], row-major (VOTES; num_classes is ignored for
+ * MEAN); per_tree_out, when given, receives tree_pd as host [trees x G].
+ * SBAG_EINVAL (nothing written, the context stays usable): a null argument (weights and
+ * per_tree_out may be NULL), an unknown kind, `feature` outside [0, num_features), G outside
+ * [1, 256], a grid that is not finite and strictly ascending, VOTES on a forest that is not
+ * gini or with num_classes below its class count, weights or per_tree_out given with VOTES,
+ * num_rows == 0 (the mean of nothing), and the argument errors of sbag_predict /
+ * sbag_predict_dataset (a subspace past the features, ds on another device).
+ * SBAG_EUNSUPPORTED: num_rows > INT32_MAX; more than 2 GB of counts (8 bytes x the forest's
+ * leaves x G).
+ * With a sorted grid a row's walk through a tree splits the grid into contiguous ranges, one per
+ * leaf reached, so a row costs one walk per tree, not G.  u8 / u16 codes whose trees (packed
+ * nodes and int32 counters [leaves][G + 1]) fit the LDS beside a tile of 512 rows go through
+ * one fused pass that keeps the counts of a tree group in LDS over a whole slice of the rows
+ * (host rows are binned against the forest's thresholds first, in row batches as in
+ * sbag_predict, the counts accumulating across batches); u32 codes, larger trees (or more than
+ * 16 384 nodes), a tree that can hold more than 8 pending ranges at once, a feature of host rows
+ * with more than 65 535 thresholds, and every call under SBAG_PD_FORCE_FALLBACK=1 (read on every
+ * call) walk global memory, one thread per row: the same integers, so the same bytes.  Only out
+ * and per_tree_out cross to the host.                                                       */
+#define SBAG_PD_MEAN 0  /* pd[g]: the mean (or weighted sum) of the trees' mean predictions  */
+#define SBAG_PD_VOTES 1 /* pd[g][c]: the fraction of (row, tree) votes for class c           */
+int sbag_partial_dependence(sbag_ctx* ctx, const sbag_forest* f, const double* X, int64_t num_rows,
+                            int32_t num_features, int32_t feature, const double* grid /* host [G] */,
+                            int32_t G, int32_t kind, int32_t num_classes,
+                            const double* weights /* host [trees] or NULL */,
+                            double* out /* host [G] or [G x num_classes] */,
+                            double* per_tree_out /* host [trees x G] or NULL */);
+int sbag_partial_dependence_dataset(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* ds,
+                                    int32_t feature, const double* grid, int32_t G, int32_t kind,
+                                    int32_t num_classes, const double* weights, double* out,
+                                    double* per_tree_out);
 /* ---- Stacking: the level-1 dataset and the two-level transform -----------------------------
  * StackingRegressor.train (ml/regression/StackingRegressor.scala:163-171) and
  * StackingClassifier.train (ml/classification/StackingClassifier.scala:164-172) map every

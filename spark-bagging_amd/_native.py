@@ -19,6 +19,7 @@ AGG_MEAN, AGG_MODE = 0, 1
 OUT_SUM, OUT_VOTES = 2, 3  # device outputs of sbag_predict_dataset_device
 RAW_VOTES, RAW_LEAF = 0, 1  # kinds of sbag_predict_raw: hard / soft voting
 W_DOT, W_CLASS = 0, 1  # kinds of sbag_predict_weighted: weighted sums / class weights
+PD_MEAN, PD_VOTES = 0, 1  # kinds of sbag_partial_dependence: mean prediction / vote fractions
 COL_F64, COL_F32, COL_U8 = 0, 1, 2  # sbag_dataset_create_columns
 
 # every symbol include/sbag.h declares (checked by tests/test_abi.py)
@@ -38,6 +39,7 @@ EXPORTED = [
     "sbag_dataset_create_stacked", "sbag_predict_stacked", "sbag_predict_stacked_dataset",
     "sbag_predict_weighted", "sbag_predict_weighted_dataset", "sbag_eval_staged",
     "sbag_predict_quantiles", "sbag_predict_quantiles_dataset", "sbag_predict_oob_quantiles",
+    "sbag_partial_dependence", "sbag_partial_dependence_dataset",
 ]
 
 
@@ -181,6 +183,8 @@ def lib():
             "sbag_predict_quantiles": [P, P, P, i64, i32, P, i32, P],
             "sbag_predict_quantiles_dataset": [P, P, P, P, i32, P],
             "sbag_predict_oob_quantiles": [P, P, P, ctypes.POINTER(SamplerParams), P, i32, P, i32, P, P],
+            "sbag_partial_dependence": [P, P, P, i64, i32, i32, P, i32, i32, i32, P, P, P],
+            "sbag_partial_dependence_dataset": [P, P, P, i32, P, i32, i32, i32, P, P, P],
             "sbag_forest_timing": [P, ctypes.POINTER(Timing)],
             "sbag_predict": [P, P, P, i64, i32, i32, P, P],
             "sbag_predict_dataset": [P, P, P, i32, P],
@@ -797,6 +801,38 @@ def predict_oob_quantiles(ctx, forest, dataset, probs, *, replacement, sample_ra
     check(lib().sbag_predict_oob_quantiles(ctx.handle, forest.handle, dataset.handle, ctypes.byref(sp), ptr(off),
                                            P, ptr(p), len(p), ptr(out), ptr(n_oob)))
     return out, n_oob
+
+
+def _pd_call(forest, grid, kind, num_classes, weights, per_tree, call):
+    g = np.ascontiguousarray(grid, np.float64).reshape(-1)
+    C = _raw_width(forest, num_classes) if kind == PD_VOTES else 0
+    out = np.zeros((len(g), C) if kind == PD_VOTES else len(g), np.float64)
+    w = None if weights is None else np.ascontiguousarray(weights, np.float64).reshape(-1)
+    if w is not None and len(w) != len(forest):
+        raise IllegalArgumentException(SBAG_EINVAL, f"{len(w)} weights for {len(forest)} trees")
+    pt = np.zeros((len(forest), len(g)), np.float64) if per_tree else None
+    check(call(ptr(g), len(g), kind, C, ptr(w), ptr(out), ptr(pt)))
+    return (out, pt) if per_tree else out
+
+
+def partial_dependence(ctx, forest, X, feature, grid, kind=0, num_classes=None, weights=None, per_tree=False):
+    """Partial dependence of the forest on global feature `feature` over host rows
+    (sbag_partial_dependence, sbag.h's rule): PD_MEAN fp64 [G] (with `weights` the in-order
+    weighted sum of the trees' means), PD_VOTES fp64 [G, num_classes] vote fractions.  With
+    per_tree (PD_MEAN) also the trees' own means, fp64 [trees, G]."""
+    X = np.ascontiguousarray(X, np.float64)
+    return _pd_call(forest, grid, kind, num_classes, weights, per_tree,
+                    lambda *tail: lib().sbag_partial_dependence(ctx.handle, forest.handle, ptr(X), X.shape[0],
+                                                                X.shape[1], int(feature), *tail))
+
+
+def partial_dependence_dataset(ctx, forest, dataset, feature, grid, kind=0, num_classes=None, weights=None,
+                               per_tree=False):
+    """partial_dependence over a device dataset (sbag_partial_dependence_dataset): the rows stay
+    resident and only the G (or trees x G) results come down."""
+    return _pd_call(forest, grid, kind, num_classes, weights, per_tree,
+                    lambda *tail: lib().sbag_partial_dependence_dataset(ctx.handle, forest.handle,
+                                                                        dataset.handle, int(feature), *tail))
 
 
 def predict_stacked(ctx, base, stack, X_or_dataset):

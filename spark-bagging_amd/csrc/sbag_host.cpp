@@ -35,6 +35,7 @@
 #include "sbag_fastmath.h"
 #include "sbag_internal.h"
 #include "sbag_mfma_plan.h"
+#include "sbag_pd_plan.h"
 #include "sbag_spread_plan.h"
 #include "sbag_stack_plan.h"
 
@@ -5964,6 +5965,320 @@ int sbag_predict_oob_quantiles(sbag_ctx* c, const sbag_forest* f, const sbag_dat
   TRY(quant_dataset(c, f, ds, probs, num_probs, R, out));
   if (n_oob_out && N > 0) TRY(d2h(c, n_oob_out, R.q.n_oob, (size_t)N));
   return SBAG_OK;
+}
+
+}  // extern "C"
+
+// ---- partial dependence on one feature (sbag_pd.hip).  A call goes through k_pd_count when the
+// codes are u8 / u16, every tree's packed nodes and difference table fit the LDS beside a row
+// tile (sbag_pd_plan.h), no tree has more than kPdMaxTreeNodes packed nodes or can hold more than
+// kPdStack pending ranges, and SBAG_PD_FORCE_FALLBACK is not set; else through k_pd_walk +
+// k_pd_prefix.  Both fill the same u64 counts, which k_pd_fold turns into the result.
+// SBAG_PD_GROUP_TREES caps the trees of a group, SBAG_PD_SLICE_TILES sets the tiles of a row
+// slice (tests; all three are read on every call).
+static int check_pd(const sbag_forest* f, int32_t feature, int32_t F, const double* grid, int32_t G,
+                    int32_t kind, int32_t num_classes, const double* weights, const double* per_tree,
+                    int64_t N) {
+  if (kind != SBAG_PD_MEAN && kind != SBAG_PD_VOTES) return fail(SBAG_EINVAL, "unknown partial dependence kind");
+  if (feature < 0 || feature >= F) return fail(SBAG_EINVAL, "feature " + std::to_string(feature) + " is outside the features");
+  if (G < 1 || G > kPdMaxGrid) return fail(SBAG_EINVAL, "the grid must hold 1 to " + std::to_string(kPdMaxGrid) + " points");
+  for (int g = 0; g < G; g++)
+    if (!std::isfinite(grid[g]) || (g > 0 && !(grid[g] > grid[g - 1])))
+      return fail(SBAG_EINVAL, "the grid must be finite and strictly ascending");
+  if (kind == SBAG_PD_VOTES) {
+    if (f->impurity != SBAG_IMPURITY_GINI) return fail(SBAG_EINVAL, "vote fractions need a gini forest");
+    if (num_classes < f->nclasses)
+      return fail(SBAG_EINVAL, "num_classes " + std::to_string(num_classes) + " is below the forest's " +
+                                   std::to_string(f->nclasses) + " classes");
+    if (weights || per_tree) return fail(SBAG_EINVAL, "vote fractions take no weights and give no per-tree output");
+  }
+  if (N == 0) return fail(SBAG_EINVAL, "partial dependence of no rows");
+  if (N > INT32_MAX) return fail(SBAG_EUNSUPPORTED, "partial dependence over more than 2^31 - 1 rows");
+  return SBAG_OK;
+}
+
+struct PdRun {
+  bool fused = false;
+  int64_t leaves = 0;   // of the forest
+  unsigned long long* cnt = nullptr;  // [leaves][G], then the votes [G][C]
+  PdCountArgs ca{};
+  int slice_knob = 0;   // SBAG_PD_SLICE_TILES, 0: the plan's
+  const DevNode* nodes = nullptr;  // general path
+  const int64_t* off = nullptr;
+  const int32_t* jcut = nullptr;
+  PdFoldArgs fa{};
+};
+
+// the plan of a pass over codes of `code_bytes` at row stride S (tc_of: a threshold in code
+// space, as plan_tiled's), uploaded with the zeroed counts; may_fuse false: the general path
+template <typename TC>
+static int pd_prepare(sbag_ctx* c, const sbag_forest* f, int32_t feature, const double* grid, int G, int kind,
+                      int C, const double* weights, int code_bytes, int S, int F, bool may_fuse, TC tc_of,
+                      PdRun& R) {
+  const int L = (int)f->trees.size();
+  const char* ffb = getenv("SBAG_PD_FORCE_FALLBACK");
+  if (ffb && atoi(ffb) != 0) may_fuse = false;
+  int max_trees = INT_MAX;
+  if (const char* e = getenv("SBAG_PD_GROUP_TREES")) max_trees = std::max(1, atoi(e));
+  if (const char* e = getenv("SBAG_PD_SLICE_TILES")) R.slice_knob = std::max(1, atoi(e));
+  // the leaves in node (pre-order) order, and s = #{g : grid[g] <= threshold} of every node that
+  // tests the feature (fp64, Spark's rule; a NaN threshold sends every point right)
+  std::vector<int64_t> leaf_off(L + 1, 0), node_off(L + 1, 0);
+  std::vector<double> leaf_val;
+  std::vector<int32_t> jcut;
+  for (int t = 0; t < L; t++) {
+    const HTree& h = f->trees[t];
+    for (const sbag_node& n : h.nodes) {
+      if (n.left < 0) leaf_val.push_back(n.prediction);
+      int32_t s = -1;
+      if (n.left >= 0 && h.sub[n.feature] == feature)
+        s = n.threshold != n.threshold ? 0 : (int32_t)(std::upper_bound(grid, grid + G, n.threshold) - grid);
+      jcut.push_back(s);
+    }
+    leaf_off[t + 1] = (int64_t)leaf_val.size();
+    node_off[t + 1] = (int64_t)jcut.size();
+  }
+  R.leaves = (int64_t)leaf_val.size();
+  const size_t cnt_words = (size_t)R.leaves * G, vote_words = kind == SBAG_PD_VOTES ? (size_t)G * C : 0;
+  if ((cnt_words + vote_words) * 8 > ((size_t)2 << 30))
+    return fail(SBAG_EUNSUPPORTED, "the leaf counts of " + std::to_string(R.leaves) + " leaves x " +
+                                       std::to_string(G) + " grid points exceed 2 GB");
+  // the fused plan: trees relaid breadth first (children adjacent) as plan_tiled's
+  std::vector<PNode> pn;
+  std::vector<int64_t> tn(L, 0), tree_nodes(L, 0), tree_leaves(L, 0);
+  std::vector<int> ends;
+  bool fused = may_fuse && F < 32768;
+  for (int t = 0; t < L && fused; t++) {
+    const HTree& h = f->trees[t];
+    const int32_t* jc = jcut.data() + node_off[t];
+    std::vector<int32_t> lf(h.nodes.size()), rt(h.nodes.size()), ord(h.nodes.size(), 0);
+    int32_t nleaf = 0;
+    for (size_t k = 0; k < h.nodes.size(); k++) {
+      lf[k] = h.nodes[k].left;
+      rt[k] = h.nodes[k].right;
+      if (lf[k] < 0) ord[k] = nleaf++;
+    }
+    if (pd_stack_need(lf.data(), rt.data(), jc, (int64_t)h.nodes.size(), G) > kPdStack) fused = false;
+    tn[t] = (int64_t)pn.size();
+    std::vector<int> order{0};
+    std::vector<int> first;  // position of a node's left child
+    for (size_t k = 0; k < order.size() && fused; k++) {
+      const sbag_node& n = h.nodes[order[k]];
+      first.push_back((int)order.size());
+      if (n.left >= 0) {
+        order.push_back(n.left);
+        order.push_back(n.right);
+      }
+      if (order.size() > (size_t)kPdMaxTreeNodes) fused = false;
+    }
+    for (size_t k = 0; k < order.size() && fused; k++) {
+      const sbag_node& n = h.nodes[order[k]];
+      PNode q{};
+      if (n.left < 0) {
+        q.a = 0x80000000u | (uint32_t)ord[order[k]];  // + the tree's first row in its group, below
+      } else if (jc[order[k]] >= 0) {
+        q.a = kPdTestsFeature | (uint32_t)first[k];
+        q.b = (uint32_t)jc[order[k]];
+      } else {
+        const int g = h.sub[n.feature];
+        const int64_t tc = tc_of(g, n.threshold);
+        if (tc + 1 >= (1 << 17)) fused = false;
+        q.a = (uint32_t)first[k];
+        q.b = ((uint32_t)g << 17) | (uint32_t)(tc + 1);
+      }
+      pn.push_back(q);
+    }
+    tree_nodes[t] = (int64_t)pn.size() - tn[t];
+    tree_leaves[t] = nleaf;
+  }
+  const size_t tile_bytes = pd_tile_lds(S * code_bytes + 4);
+  fused = fused && pd_plan_groups(tree_nodes, tree_leaves, G, tile_bytes, max_trees, ends);
+  R.fused = fused;
+  double* d_lv;
+  int64_t* d_lo;
+  TRY(ws_typed(c, "pdep_cnt", cnt_words + vote_words, &R.cnt));
+  TRY(ws_typed(c, "pdep_lval", std::max<size_t>(leaf_val.size(), 1), &d_lv));
+  TRY(ws_typed(c, "pdep_loff", leaf_off.size(), &d_lo));
+  TRY(h2d(c, d_lv, leaf_val.data(), leaf_val.size()));
+  TRY(h2d(c, d_lo, leaf_off.data(), leaf_off.size()));
+  launch_pd_zero(c->stream, R.cnt, (int64_t)(cnt_words + vote_words));
+  HIP_TRY(hipGetLastError());
+  R.fa.cnt = R.cnt;
+  R.fa.leaf_off = d_lo;
+  R.fa.leaf_val = d_lv;
+  R.fa.L = L;
+  R.fa.G = G;
+  R.fa.votes_kind = kind == SBAG_PD_VOTES;
+  R.fa.C = C;
+  R.fa.votes = R.cnt + cnt_words;
+  if (weights) {
+    double* d_w;
+    TRY(ws_typed(c, "pdep_w", (size_t)L, &d_w));
+    TRY(h2d(c, d_w, weights, (size_t)L));
+    R.fa.weights = d_w;
+  }
+  TRY(ws_typed(c, "pdep_tree", (size_t)L * G, &R.fa.tree_pd));
+  TRY(ws_typed(c, "pdep_out", (size_t)G * std::max(C, 1), &R.fa.out));
+  if (fused) {
+    std::vector<PdGroup> groups;
+    size_t group_bytes = 0;
+    int t0 = 0;
+    for (int t1 : ends) {
+      PdGroup g{};
+      g.t0 = t0;
+      g.t1 = t1;
+      g.n0 = tn[t0];
+      g.l0 = leaf_off[t0];
+      g.nn = (int32_t)(tn[t1 - 1] + tree_nodes[t1 - 1] - tn[t0]);
+      g.nl = (int32_t)(leaf_off[t1] - leaf_off[t0]);
+      for (int t = t0; t < t1; t++)  // a leaf's row in the group's table
+        for (int64_t k = tn[t]; k < tn[t] + tree_nodes[t]; k++)
+          if (pn[k].a & 0x80000000u) pn[k].a += (uint32_t)(leaf_off[t] - g.l0);
+      group_bytes = std::max(group_bytes, (size_t)g.nn * 8 + (size_t)g.nl * (G + 1) * 4);
+      groups.push_back(g);
+      t0 = t1;
+    }
+    PNode* d_pn;
+    int64_t* d_tn;
+    PdGroup* d_gr;
+    TRY(ws_typed(c, "pdep_nodes", std::max<size_t>(pn.size(), 1), &d_pn));
+    TRY(ws_typed(c, "pdep_tn", tn.size(), &d_tn));
+    TRY(ws_typed(c, "pdep_groups", groups.size(), &d_gr));
+    TRY(h2d(c, d_pn, pn.data(), pn.size()));
+    TRY(h2d(c, d_tn, tn.data(), tn.size()));
+    TRY(h2d(c, d_gr, groups.data(), groups.size()));
+    R.ca.code_bytes = code_bytes;
+    R.ca.S = S;
+    R.ca.nodes = d_pn;
+    R.ca.tree_node = d_tn;
+    R.ca.groups = d_gr;
+    R.ca.ngroups = (int)groups.size();
+    R.ca.G = G;
+    R.ca.tile_bytes = (int32_t)tile_bytes;
+    R.ca.group_bytes = (int32_t)((group_bytes + 15) & ~(size_t)15);
+    R.ca.cnt = R.cnt;
+    return SBAG_OK;
+  }
+  int32_t* d_jc;
+  TRY(upload_forest(c, f, &R.nodes, &R.off));
+  TRY(ws_typed(c, "pdep_jcut", std::max<size_t>(jcut.size(), 1), &d_jc));
+  TRY(h2d(c, d_jc, jcut.data(), jcut.size()));
+  R.jcut = d_jc;
+  return SBAG_OK;
+}
+
+// k_pd_count over n rows of codes
+static int pd_count(sbag_ctx* c, PdRun& R, const void* codes, int64_t n) {
+  int cus = 256;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
+  R.ca.codes = codes;
+  R.ca.N = n;
+  const int64_t ntiles = (n + kPdTileRows - 1) / kPdTileRows;
+  R.ca.slice_tiles = R.slice_knob ? R.slice_knob : pd_slice_tiles(ntiles, R.ca.ngroups, cus);
+  launch_pd_count(c->stream, R.ca);
+  HIP_TRY(hipGetLastError());
+  return SBAG_OK;
+}
+
+// the counts are complete: fold, and the results to the host
+static int pd_finish(sbag_ctx* c, PdRun& R, int64_t N, double* out, double* per_tree) {
+  if (!R.fused) {
+    launch_pd_prefix(c->stream, R.cnt, R.leaves, R.fa.G);
+    HIP_TRY(hipGetLastError());
+  }
+  R.fa.N = N;
+  launch_pd_fold(c->stream, R.fa);
+  HIP_TRY(hipGetLastError());
+  if (per_tree) TRY(d2h(c, per_tree, R.fa.tree_pd, (size_t)R.fa.L * R.fa.G));
+  TRY(d2h(c, out, R.fa.out, (size_t)R.fa.G * (R.fa.votes_kind ? R.fa.C : 1)));
+  return SBAG_OK;
+}
+
+extern "C" {
+
+int sbag_partial_dependence(sbag_ctx* c, const sbag_forest* f, const double* X, int64_t N, int32_t F,
+                            int32_t feature, const double* grid, int32_t G, int32_t kind, int32_t num_classes,
+                            const double* weights, double* out, double* per_tree) {
+  if (!c || !f || !X || !grid || !out || N < 0 || F <= 0) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(check_pd(f, feature, F, grid, G, kind, num_classes, weights, per_tree, N));
+  for (const HTree& t : f->trees)
+    for (int32_t g : t.sub)
+      if (g >= F) return fail(SBAG_EINVAL, "feature vector shorter than a subspace index");
+  HIP_TRY(hipSetDevice(c->device));
+  // rows are binned on the device against the forest's own thresholds, as in sbag_predict
+  std::vector<std::vector<double>> T(F);
+  for (const HTree& t : f->trees)
+    for (const sbag_node& n : t.nodes)
+      if (n.left >= 0) T[t.sub[n.feature]].push_back(n.threshold);
+  std::vector<int64_t> toff(F + 1, 0);
+  size_t max_thr = 0;
+  for (int g = 0; g < F; g++) {
+    std::sort(T[g].begin(), T[g].end());
+    T[g].erase(std::unique(T[g].begin(), T[g].end()), T[g].end());
+    toff[g + 1] = toff[g] + (int64_t)T[g].size();
+    max_thr = std::max(max_thr, T[g].size());
+  }
+  const int32_t Sq = (F + 15) / 16 * 16;
+  PdRun R;
+  TRY(pd_prepare(c, f, feature, grid, G, kind, num_classes, weights, 2, Sq, F, max_thr <= 65535,
+                 [&](int g, double thr) {
+                   return (int64_t)(std::lower_bound(T[g].begin(), T[g].end(), thr) - T[g].begin());
+                 }, R));
+  double* d_X;
+  if (R.fused) {
+    std::vector<double> tv((size_t)std::max<int64_t>(toff[F], 1));
+    for (int g = 0; g < F; g++) std::copy(T[g].begin(), T[g].end(), tv.begin() + toff[g]);
+    double* d_T;
+    int64_t* d_toff;
+    TRY(ws_typed(c, "pq_thr", tv.size(), &d_T));
+    TRY(ws_typed(c, "pq_off", toff.size(), &d_toff));
+    TRY(h2d(c, d_T, tv.data(), tv.size()));
+    TRY(h2d(c, d_toff, toff.data(), toff.size()));
+    int64_t batch = std::max<int64_t>(1, std::min<int64_t>(N, ((int64_t)2 << 30) / (8 * (int64_t)F)));
+    if (const char* e = getenv("SBAG_PREDICT_BATCH_ROWS")) batch = std::max<int64_t>(1, std::min<int64_t>(batch, atoll(e)));
+    uint16_t* d_codes;
+    TRY(ws_typed(c, "pX", (size_t)batch * F, &d_X));
+    TRY(ws_typed(c, "pq_codes", (size_t)batch * Sq, &d_codes));
+    for (int64_t r0 = 0; r0 < N; r0 += batch) {  // the counts keep accumulating across batches
+      const int64_t n = std::min(batch, N - r0);
+      HIP_TRY(hipMemcpyAsync(d_X, X + r0 * F, (size_t)n * F * 8, hipMemcpyHostToDevice, c->stream));
+      launch_quantize(c->stream, d_X, n, F, d_T, d_toff, d_codes, Sq);
+      TRY(pd_count(c, R, d_codes, n));
+    }
+  } else {
+    TRY(ws_typed(c, "pX", (size_t)N * F, &d_X));
+    TRY(h2d(c, d_X, X, (size_t)N * F));
+    launch_pd_walk(c->stream, d_X, nullptr, 1, nullptr, nullptr, N, F, F, R.nodes, R.off, R.jcut,
+                   R.fa.leaf_off, R.fa.L, G, R.cnt);
+    HIP_TRY(hipGetLastError());
+  }
+  return pd_finish(c, R, N, out, per_tree);
+}
+
+int sbag_partial_dependence_dataset(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds, int32_t feature,
+                                    const double* grid, int32_t G, int32_t kind, int32_t num_classes,
+                                    const double* weights, double* out, double* per_tree) {
+  if (!c || !f || !ds || !grid || !out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(check_pd(f, feature, ds->F, grid, G, kind, num_classes, weights, per_tree, ds->N));
+  TRY(check_quant_dataset(c, f, ds));
+  HIP_TRY(hipSetDevice(c->device));
+  PdRun R;
+  // TreePoint's `value <= threshold` in the dataset's code space (dict sorted ascending)
+  TRY(pd_prepare(c, f, feature, grid, G, kind, num_classes, weights, ds->code_bytes, ds->S, ds->F,
+                 ds->code_bytes != 4, [&](int g, double thr) {
+                   const std::vector<double>& d = ds->dict[g];
+                   return (int64_t)(std::upper_bound(d.begin(), d.end(), thr) - d.begin()) - 1;
+                 }, R));
+  if (R.fused) {
+    TRY(pd_count(c, R, ds->d_codes, ds->N));
+  } else {
+    launch_pd_walk(c->stream, nullptr, ds->d_codes, ds->code_bytes, ds->d_dict, ds->d_dict_off, ds->N, ds->F,
+                   ds->S, R.nodes, R.off, R.jcut, R.fa.leaf_off, R.fa.L, G, R.cnt);
+    HIP_TRY(hipGetLastError());
+  }
+  return pd_finish(c, R, ds->N, out, per_tree);
 }
 
 }  // extern "C"

@@ -459,6 +459,58 @@ void launch_quant_walk(hipStream_t st, const double* X, const void* codes, int c
                        uint32_t* keys);
 // k_quant_select: a wave per row over keys [L][n]; q.out / q.n_oob are the batch's first row's
 void launch_quant_select(hipStream_t st, const uint32_t* keys, int64_t n, int L, const QuantArgs& q);
+// ---- partial dependence on one feature (sbag_pd.hip): the leaf-occupancy counts
+// cnt[leaf][g] of sbag.h's rule, u64 [leaves of the forest][G], a tree's leaves in node
+// (pre-order) order from leaf_off[t], and their fold into tree_pd / votes / pd.
+// A packed node of k_pd_count (PNode): leaf a = 0x80000000 | the leaf's row in its group's
+// difference table; a node that tests the feature a = 0x40000000 | left child,
+// b = s = #{g : grid[g] <= threshold}; any other node as k_predict_tiled's.
+constexpr uint32_t kPdTestsFeature = 0x40000000u;
+struct PdGroup {        // consecutive trees whose nodes + difference tables fit the LDS
+  int32_t t0, t1;       // trees [t0, t1)
+  int32_t nn, nl;       // packed nodes and leaves of the group
+  int64_t n0, l0;       // its first packed node; its first leaf among the forest's
+};
+struct PdCountArgs {
+  const void* codes;    // [N][S] u8 / u16
+  int32_t code_bytes, S;
+  int64_t N;
+  const PNode* nodes;
+  const int64_t* tree_node;  // [L] first packed node of each tree
+  const PdGroup* groups;
+  int32_t ngroups, G;
+  int64_t slice_tiles;  // 512-row tiles of a row slice (sbag_pd_plan.h)
+  int32_t tile_bytes;   // LDS bytes of the staged tile
+  int32_t group_bytes;  // LDS bytes of the largest group
+  unsigned long long* cnt;
+};
+// k_pd_count: grid (row slices, groups); the counts of the N rows are added to a.cnt
+void launch_pd_count(hipStream_t st, const PdCountArgs& a);
+// k_pd_walk: one thread per row of a batch of n over DevNodes in global memory (X fp64 rows, or
+// codes + dictionaries as launch_predict); jcut[node] = s for a node that tests the feature,
+// else -1.  Adds +1 at cnt[leaf][lo] and -1 at cnt[leaf][hi] (mod 2^64): differences, which
+// launch_pd_prefix turns into counts once every batch has run.
+void launch_pd_walk(hipStream_t st, const double* X, const void* codes, int code_bytes, const double* dict,
+                    const int64_t* dict_off, int64_t n, int32_t F, int32_t S, const DevNode* nodes,
+                    const int64_t* tree_off, const int32_t* jcut, const int64_t* leaf_off, int L, int G,
+                    unsigned long long* cnt);
+void launch_pd_prefix(hipStream_t st, unsigned long long* cnt, int64_t leaves, int G);
+struct PdFoldArgs {
+  const unsigned long long* cnt;
+  const int64_t* leaf_off;   // [L + 1]
+  const double* leaf_val;    // the leaves' predictions, as cnt's rows
+  const double* weights;     // [L] or null (mean)
+  int32_t L, G;
+  int32_t votes_kind;        // 0: SBAG_PD_MEAN, 1: SBAG_PD_VOTES
+  int32_t C;                 // votes: columns of out
+  int64_t N;
+  double* tree_pd;           // mean: [L][G]
+  unsigned long long* votes; // votes: [G][C], zeroed
+  double* out;               // [G] or [G][C]
+};
+void launch_pd_fold(hipStream_t st, const PdFoldArgs& a);
+// zeroes n 64-bit words
+void launch_pd_zero(hipStream_t st, unsigned long long* p, int64_t n);
 // ---- out-of-bag predictions under permuted features (sbag_oobperm.hip): slot k of a
 // feature batch is sbag_predict_oob with feature feat[k] of row r taken from row src[k][r].
 // Between learner batches a slot's state lives in global memory as the baseline's does:

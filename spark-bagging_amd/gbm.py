@@ -33,7 +33,7 @@ from . import _native as nat
 from . import persistence as sp
 from .libsvm import is_sparse
 from .ml import (DecisionTreeModel, DecisionTreeRegressor, Frame, Params, _DecisionTreeEstimator,
-                 _in_range01, java_string_hash)
+                 _in_range01, java_string_hash, partial_dependence)
 
 SUPPORTED_LOSSES = ("squared", "absolute", "huber", "quantile")
 DOUBLE_MAX = np.finfo(np.float64).max
@@ -178,6 +178,14 @@ class GBMRegressionModel(_GBMParams):
 
     def predict(self, features):
         return float(self.transform(np.asarray(features, np.float64)[None, :])[0])
+
+    def partialDependence(self, dataset, feature, grid=None, numPoints=32, perTree=False, device=0):
+        """(grid, pd): the model's mean prediction over the rows with feature `feature` set to
+        each grid value: the in-order weighted sum of the boosters' means (made on the device)
+        plus const.  perTree: pd is (pd [G], the boosters' own means [trees, G])."""
+        grid, pd = partial_dependence(self.native_forest(), dataset, feature, grid, numPoints, nat.PD_MEAN,
+                                      weights=self.weights, perTree=perTree, device=device)
+        return (grid, (pd[0] + self.const, pd[1])) if perTree else (grid, pd + self.const)
 
     # ---- persistence: GBMRegressionModelWriter (GBMRegressor.scala:535-559)
     def save(self, path):

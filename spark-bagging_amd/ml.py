@@ -869,6 +869,37 @@ class _BaggingModel(_BaggingParams):
         return m
 
 
+def partial_dependence(forest, dataset, feature, grid, numPoints, kind, weights=None, perTree=False, device=0):
+    """(grid, pd) of `forest` on global feature `feature` (sbag_partial_dependence(_dataset)).
+    `dataset` as in transform; a DeviceDataset stays resident.  grid None: the distinct values
+    of np.quantile(x_feature, np.linspace(0.05, 0.95, numPoints))."""
+    feature = int(feature)
+    resident = isinstance(dataset, nat.DeviceDataset)
+    if resident:
+        X, ctx = None, dataset.ctx
+    else:
+        ctx = nat.default_context(device)
+        X = dataset.features if isinstance(dataset, Frame) else dataset
+        if is_sparse(X):
+            X = X.toarray() if hasattr(X, "toarray") else X.to_dense()
+        X = np.asarray(X, np.float64)
+        if X.ndim == 1:
+            X = X[None, :]
+    n, F = dataset.shape if resident else X.shape
+    if not 0 <= feature < F:
+        raise nat.IllegalArgumentException(nat.SBAG_EINVAL, f"feature {feature} is outside the {F} features")
+    if grid is None:
+        if n == 0:
+            raise nat.IllegalArgumentException(nat.SBAG_EINVAL, "partial dependence of no rows")
+        column = dataset.features(0, n)[:, feature] if resident else X[:, feature]
+        grid = np.unique(np.quantile(column, np.linspace(0.05, 0.95, int(numPoints))))
+    grid = np.ascontiguousarray(grid, np.float64).reshape(-1)
+    if resident:
+        return grid, nat.partial_dependence_dataset(ctx, forest, dataset, feature, grid, kind, weights=weights,
+                                                    per_tree=perTree)
+    return grid, nat.partial_dependence(ctx, forest, X, feature, grid, kind, weights=weights, per_tree=perTree)
+
+
 class BaggingRegressionModel(_BaggingModel):
     _agg = nat.AGG_MEAN
     _spark_class = "org.apache.spark.ml.regression.BaggingRegressionModel"
@@ -896,6 +927,13 @@ class BaggingRegressionModel(_BaggingModel):
         if X.ndim == 1:
             X = X[None, :]
         return nat.predict_quantiles(ctx, forest, X, probabilities)
+
+    def partialDependence(self, dataset, feature, grid=None, numPoints=32, perTree=False, device=0):
+        """(grid, pd): the ensemble's mean prediction over the rows of `dataset` with feature
+        `feature` set to each grid value (randomForest's partialPlot), counted on the device in
+        one walk per row and tree.  perTree: pd is (pd [G], tree_pd [trees, G])."""
+        return partial_dependence(self.native_forest(), dataset, feature, grid, numPoints, nat.PD_MEAN,
+                                  perTree=perTree, device=device)
 
     def predictInterval(self, dataset, coverage=0.9, device=0):
         """(lower, upper): the ensemble's quantiles at (1 - coverage) / 2 and (1 + coverage) / 2."""
@@ -1038,6 +1076,12 @@ class BaggingClassificationModel(_BaggingModel):
         else:
             y = dataset.label if isinstance(dataset, Frame) else dataset[1]
         return oob_log_loss(proba, n_oob, y)
+
+    def partialDependence(self, dataset, feature, grid=None, numPoints=32, device=0):
+        """(grid, pd [G, numClasses]): the fraction of the (row, tree) votes each class gets with
+        feature `feature` of every row set to each grid value (hard voting)."""
+        return partial_dependence(self.native_forest(), dataset, feature, grid, numPoints, nat.PD_VOTES,
+                                  device=device)
 
 
 class BaggingRegressor(_BaggingEstimator):
