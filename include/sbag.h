@@ -581,6 +581,60 @@ int sbag_partial_dependence_dataset(sbag_ctx* ctx, const sbag_forest* f, const s
                                     int32_t feature, const double* grid, int32_t G, int32_t kind,
                                     int32_t num_classes, const double* weights, double* out,
                                     double* per_tree_out);
+/* ---- per-row feature contributions: path-dependent TreeSHAP (XGBoost's pred_contribs,
+ * LightGBM's predict_contrib, shap.TreeExplainer), in the per-leaf form of Lundberg's Algorithm 2.
+ * out[r][g] is the contribution of global feature g to row r's prediction, out[r][num_features]
+ * the bias, the ensemble's expected value; a row sums to its prediction up to rounding.  All
+ * arithmetic is fp64 and every operation below is rounded on its own: no FMA, no reassociation.
+ * Cover.  c(n) is stats[n][0] for a variance tree, the left-to-right sum of stats[n][0 .. ns_t)
+ *   for a gini tree: the node's weighted row count, which sbag_fit, sbag_fit_bag,
+ *   sbag_fit_booster and sbag_forest_create_stats keep.
+ * Leaf value v_l.  class_index == -1 (a variance forest): the leaf's prediction.  class_index
+ *   >= 0 (a gini forest, an index below sbag_forest_num_classes): st[class_index] / total as
+ *   SBAG_RAW_LEAF, 0.0 when class_index >= ns_t.  vw_l = v_l when weights == NULL, else
+ *   v_l * weights[t].
+ * Paths.  For each leaf l of tree t, in pre-order, with its root-to-leaf path n_0 .. n_d:
+ *   e_1 .. e_m are the distinct global features the path tests, in order of first appearance (a
+ *   single-leaf tree has m = 0); z_k is the product, in path order, of c(n_{j+1}) / c(n_j) over
+ *   the nodes n_j that test e_k (the first factor starts the product); o_k(r) = 1 if row r goes
+ *   the path's way at every one of those nodes (left iff value <= threshold,
+ *   Split.shouldGoLeft), else 0; rz_k = 1.0 / z_k; d_k = 1.0 - z_k when o_k = 1, -z_k when
+ *   o_k = 0.
+ * Weights.  Q(a, b) = (double)a / (double)b.  pw[0] = 1.0, every other pw 0.0.  For u = 1 .. m,
+ *   with `old` the values before the step, for j = 0 .. u:
+ *     pw[j] = (z_u * old[j]) * Q(u - j, u + 1), and then, only when o_u = 1 and j > 0,
+ *     pw[j] = pw[j] + old[j - 1] * Q(j, u + 1).
+ * Unwound sum of element k.
+ *   o_k = 1: next = pw[m], total = 0.0; for i = m - 1 down to 0: tmp = next * Q(m + 1, i + 1);
+ *            total = total + tmp; next = pw[i] - (tmp * z_k) * Q(m - i, m + 1).
+ *   o_k = 0: total = 0.0; for i = m - 1 down to 0:
+ *            total = total + (pw[i] * rz_k) * Q(m + 1, m - i).
+ * Accumulation.  acc[0 .. F] starts at +0.0.  Over the trees in forest order and the leaves in
+ *   pre-order: for k = 1 .. m: acc[e_k] = acc[e_k] + (total_k * d_k) * vw_l; then
+ *   acc[F] = acc[F] + b, b = vw_l multiplied by z_1, z_2, .., z_m in that order.
+ *   out[r][g] = acc[g] / (double)trees when weights == NULL (the bagging mean), else acc[g]: the
+ *   caller adds `const` or divides by sumWeights.  A feature no tree tests is +0.0; the bias
+ *   column is the same for every row.
+ * SBAG_EINVAL (nothing written, the context stays usable): a null argument (weights may be
+ * NULL); class_index == -1 on a gini forest, >= 0 on a variance forest, below -1 or out of
+ * range; a tree without stats; a node whose cover is not finite and > 0; the argument errors of
+ * sbag_predict / sbag_predict_dataset.  num_rows == 0 is SBAG_OK.  SBAG_EUNSUPPORTED: a path
+ * with more than 64 distinct features; a packed path table over 2 GB (24 bytes a leaf, 40 an
+ * element of a path).
+ * u8 / u16 codes and forests whose paths test at most 15 distinct features go through one fused
+ * pass: a lane group per (row, leaf path) with the path's permutation weights across the lanes
+ * and the accumulators of a row tile in LDS (host rows are binned against the forest's thresholds
+ * first, in row batches as in sbag_predict).  u32 codes, a path with more features, a feature
+ * count whose 16-row tile does not fit the LDS, a feature of host rows with more than 65 535
+ * thresholds and every call under SBAG_CONTRIB_FORCE_FALLBACK=1 (read on every call) take one
+ * thread per row over the same path table: the same operations in the same order, so the same
+ * bytes.                                                                                     */
+int sbag_predict_contributions(sbag_ctx* ctx, const sbag_forest* f, const double* X, int64_t num_rows,
+                               int32_t num_features, int32_t class_index,
+                               const double* weights /* host [trees] or NULL */,
+                               double* out /* host [num_rows x (num_features + 1)], row-major */);
+int sbag_predict_contributions_dataset(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* ds,
+                                       int32_t class_index, const double* weights, double* out);
 /* ---- Stacking: the level-1 dataset and the two-level transform -----------------------------
  * StackingRegressor.train (ml/regression/StackingRegressor.scala:163-171) and
  * StackingClassifier.train (ml/classification/StackingClassifier.scala:164-172) map every

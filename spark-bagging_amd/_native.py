@@ -40,6 +40,7 @@ EXPORTED = [
     "sbag_predict_weighted", "sbag_predict_weighted_dataset", "sbag_eval_staged",
     "sbag_predict_quantiles", "sbag_predict_quantiles_dataset", "sbag_predict_oob_quantiles",
     "sbag_partial_dependence", "sbag_partial_dependence_dataset",
+    "sbag_predict_contributions", "sbag_predict_contributions_dataset",
 ]
 
 
@@ -185,6 +186,8 @@ def lib():
             "sbag_predict_oob_quantiles": [P, P, P, ctypes.POINTER(SamplerParams), P, i32, P, i32, P, P],
             "sbag_partial_dependence": [P, P, P, i64, i32, i32, P, i32, i32, i32, P, P, P],
             "sbag_partial_dependence_dataset": [P, P, P, i32, P, i32, i32, i32, P, P, P],
+            "sbag_predict_contributions": [P, P, P, i64, i32, i32, P, P],
+            "sbag_predict_contributions_dataset": [P, P, P, i32, P, P],
             "sbag_forest_timing": [P, ctypes.POINTER(Timing)],
             "sbag_predict": [P, P, P, i64, i32, i32, P, P],
             "sbag_predict_dataset": [P, P, P, i32, P],
@@ -833,6 +836,37 @@ def partial_dependence_dataset(ctx, forest, dataset, feature, grid, kind=0, num_
     return _pd_call(forest, grid, kind, num_classes, weights, per_tree,
                     lambda *tail: lib().sbag_partial_dependence_dataset(ctx.handle, forest.handle,
                                                                         dataset.handle, int(feature), *tail))
+
+
+def _contrib_weights(forest, weights):
+    w = None if weights is None else np.ascontiguousarray(weights, np.float64).reshape(-1)
+    if w is not None and len(w) != len(forest):
+        raise IllegalArgumentException(SBAG_EINVAL, f"{len(w)} weights for {len(forest)} trees")
+    return w
+
+
+def predict_contributions(ctx, forest, X, class_index=-1, weights=None):
+    """Per-row feature contributions (TreeSHAP, sbag_predict_contributions, sbag.h's rule) over
+    host rows: fp64 [N, F + 1], column g the contribution of global feature g, column F the bias.
+    class_index -1: a variance forest's predictions; >= 0: that class's leaf fraction of a gini
+    forest.  weights None: the mean over the trees; else the in-order weighted sum."""
+    X = np.ascontiguousarray(X, np.float64)
+    w = _contrib_weights(forest, weights)
+    out = np.zeros((X.shape[0], X.shape[1] + 1), np.float64)
+    check(lib().sbag_predict_contributions(ctx.handle, forest.handle, ptr(X), X.shape[0], X.shape[1],
+                                           int(class_index), ptr(w), ptr(out)))
+    return out
+
+
+def predict_contributions_dataset(ctx, forest, dataset, class_index=-1, weights=None):
+    """predict_contributions over a device dataset (sbag_predict_contributions_dataset): the rows
+    stay resident and only the [N, F + 1] results come down."""
+    w = _contrib_weights(forest, weights)
+    n, F = dataset.shape
+    out = np.zeros((n, F + 1), np.float64)
+    check(lib().sbag_predict_contributions_dataset(ctx.handle, forest.handle, dataset.handle, int(class_index),
+                                                   ptr(w), ptr(out)))
+    return out
 
 
 def predict_stacked(ctx, base, stack, X_or_dataset):

@@ -6451,6 +6451,270 @@ int sbag_predict_weighted_dataset(sbag_ctx* c, const sbag_forest* f, const sbag_
   return SBAG_OK;
 }
 
+}  // extern "C"
+
+// ---- per-row feature contributions (sbag_contrib.hip, sbag_contrib_plan.h; the rule is
+// sbag.h's).  The forest is packed once per call into a path table; a call goes through
+// k_contrib_tiled when the codes are u8 / u16, no path tests more than 15 distinct features, a
+// tile of 16 rows fits the LDS and SBAG_CONTRIB_FORCE_FALLBACK is not set (read on every call),
+// else through k_contrib_walk.
+struct ContribPlan {
+  std::vector<ContribLeaf> leaves;
+  std::vector<ContribElemF> elems;  // value space; contrib_prepare turns them into codes
+  int M = 0;                        // the largest m
+  double bias = 0.0;
+};
+
+// validates the call against the forest and packs every root-to-leaf path
+static int contrib_paths(const sbag_forest* f, int32_t class_index, const double* weights, ContribPlan& P) {
+  const int L = (int)f->trees.size();
+  const bool gini = f->impurity == SBAG_IMPURITY_GINI;
+  if (class_index == -1 ? gini : (!gini || class_index < 0 || class_index >= f->nclasses))
+    return fail(SBAG_EINVAL, "class_index " + std::to_string(class_index) + " does not fit the forest: -1 for a "
+                             "variance forest, a class below the class count for a gini forest");
+  const double inf = std::numeric_limits<double>::infinity();
+  double acc = 0.0;
+  std::vector<double> cover;
+  std::vector<int32_t> path;                   // node ids from the root to the current node
+  std::vector<std::pair<int32_t, int>> todo;   // (node, depth), pre-order
+  std::vector<ContribElemF> els;
+  for (int t = 0; t < L; t++) {
+    const HTree& h = f->trees[t];
+    if (h.ns <= 0 || h.stats.size() != h.nodes.size() * (size_t)h.ns)
+      return fail(SBAG_EINVAL, "tree " + std::to_string(t) + " carries no stats (sbag_forest_create_stats keeps them)");
+    cover.assign(h.nodes.size(), 0.0);
+    for (size_t i = 0; i < h.nodes.size(); i++) {
+      const double* st = h.stats.data() + i * h.ns;
+      double cv = st[0];
+      if (gini)
+        for (int k = 1; k < h.ns; k++) cv = cv + st[k];
+      if (!(std::isfinite(cv) && cv > 0))
+        return fail(SBAG_EINVAL, "tree " + std::to_string(t) + ", node " + std::to_string(i) +
+                                     ": the cover is not finite and positive");
+      cover[i] = cv;
+    }
+    todo.assign(1, {0, 0});
+    while (!todo.empty()) {
+      const auto [i, d] = todo.back();
+      todo.pop_back();
+      path.resize(d);
+      path.push_back(i);
+      const sbag_node& nd = h.nodes[i];
+      if (nd.left >= 0) {
+        todo.push_back({nd.right, d + 1});
+        todo.push_back({nd.left, d + 1});
+        continue;
+      }
+      els.clear();
+      for (int j = 0; j < d; j++) {
+        const sbag_node& p = h.nodes[path[j]];
+        const int32_t g = h.sub[p.feature];
+        const double ratio = cover[path[j + 1]] / cover[path[j]];
+        size_t k = 0;
+        while (k < els.size() && els[k].feat != g) k++;
+        if (k == els.size())
+          els.push_back(ContribElemF{g, 0, -inf, inf, ratio, 0.0});
+        else
+          els[k].z = els[k].z * ratio;
+        if (path[j + 1] == p.left)
+          els[k].hi = std::min(els[k].hi, p.threshold);
+        else
+          els[k].lo = std::max(els[k].lo, p.threshold);
+      }
+      if (els.size() > (size_t)kContribMaxM)
+        return fail(SBAG_EUNSUPPORTED, "a path of tree " + std::to_string(t) + " tests more than " +
+                                           std::to_string(kContribMaxM) + " distinct features");
+      double v = nd.prediction;
+      if (gini) {  // SBAG_RAW_LEAF's fraction (the cover is the same left-to-right total, > 0)
+        const double* st = h.stats.data() + (size_t)i * h.ns;
+        v = class_index < h.ns ? st[class_index] / cover[i] : 0.0;
+      }
+      const double vw = weights ? v * weights[t] : v;
+      double b = vw;
+      for (ContribElemF& e : els) {
+        e.rz = 1.0 / e.z;
+        b = b * e.z;
+      }
+      acc = acc + b;
+      P.leaves.push_back(ContribLeaf{(int32_t)P.elems.size(), (int32_t)els.size(), vw, b});
+      P.elems.insert(P.elems.end(), els.begin(), els.end());
+      P.M = std::max(P.M, (int)els.size());
+      if (P.leaves.size() * sizeof(ContribLeaf) + P.elems.size() * sizeof(ContribElemF) > kContribTableCap)
+        return fail(SBAG_EUNSUPPORTED, "the packed path table is over 2 GB");
+    }
+  }
+  P.bias = weights ? acc : acc / (double)L;
+  return SBAG_OK;
+}
+
+struct ContribRun {
+  bool tiled = false;
+  ContribArgs a{};  // codes / N / out set per launch
+};
+
+// uploads the plan for codes of `code_bytes` at row stride S (tc_of: a threshold in code space,
+// as plan_tiled's); may_tile false: the general path
+template <typename TC>
+static int contrib_prepare(sbag_ctx* c, const ContribPlan& P, int trees, int code_bytes, int S, int F,
+                           bool may_tile, TC tc_of, ContribRun& R) {
+  const char* ffb = getenv("SBAG_CONTRIB_FORCE_FALLBACK");
+  if (ffb && atoi(ffb) != 0) may_tile = false;
+  const int rows = code_bytes == 4 ? 0 : contrib_tile_rows(S * code_bytes + 4, F, P.M);
+  R.tiled = may_tile && P.M <= kContribTiledM && rows > 0;
+  ContribArgs& a = R.a;
+  a.code_bytes = code_bytes;
+  a.S = S;
+  a.F = F;
+  a.M = P.M;
+  a.rows = rows;
+  a.lanes = contrib_lanes(P.M);
+  a.trees = trees;
+  a.bias = P.bias;
+  a.nleaves = (int64_t)P.leaves.size();
+  const int Q2 = P.M + 2;
+  std::vector<double> q(contrib_q_count(P.M), 0.0);
+  for (int b = 1; b < Q2; b++)
+    for (int n = 0; n < Q2; n++) q[(size_t)b * Q2 + n] = (double)n / (double)b;
+  double* d_q;
+  ContribLeaf* d_leaves;
+  TRY(ws_typed(c, "pc_q", q.size(), &d_q));
+  TRY(ws_typed(c, "pc_leaves", P.leaves.size(), &d_leaves));
+  TRY(h2d(c, d_q, q.data(), q.size()));
+  TRY(h2d(c, d_leaves, P.leaves.data(), P.leaves.size()));
+  a.q = d_q;
+  a.leaves = d_leaves;
+  const size_t ne = std::max<size_t>(P.elems.size(), 1);
+  if (!R.tiled) {
+    ContribElemF* d_e;
+    TRY(ws_typed(c, "pc_elems", ne, &d_e));
+    TRY(h2d(c, d_e, P.elems.data(), P.elems.size()));
+    a.elems = d_e;
+    return SBAG_OK;
+  }
+  // lo < v <= hi in code space: tc_of(thr) is the largest code whose value is <= thr
+  std::vector<ContribElem> ce(P.elems.size());
+  for (size_t k = 0; k < ce.size(); k++) {
+    const ContribElemF& e = P.elems[k];
+    const int64_t lo = std::isinf(e.lo) ? 0 : (int64_t)tc_of(e.feat, e.lo) + 1;
+    const int64_t hi = std::isinf(e.hi) ? 65535 : std::min<int64_t>((int64_t)tc_of(e.feat, e.hi), 65535);
+    const bool empty = lo > hi;
+    ce[k] = ContribElem{e.feat, (uint16_t)(empty ? 1 : lo), (uint16_t)(empty ? 0 : hi), e.z, e.rz};
+  }
+  ContribElem* d_e;
+  TRY(ws_typed(c, "pc_elems", ne, &d_e));
+  TRY(h2d(c, d_e, ce.data(), ce.size()));
+  a.elems = d_e;
+  return SBAG_OK;
+}
+
+// rows of a batch: its [rows][F + 1] results within 2 GB, as the other calls' device buffers
+static int64_t contrib_batch_rows(int64_t N, int F) {
+  int64_t batch = std::max<int64_t>(1, std::min<int64_t>(N, ((int64_t)2 << 30) / (8 * ((int64_t)F + 1))));
+  if (const char* e = getenv("SBAG_PREDICT_BATCH_ROWS")) batch = std::max<int64_t>(1, std::min<int64_t>(batch, atoll(e)));
+  return batch;
+}
+
+extern "C" {
+
+int sbag_predict_contributions(sbag_ctx* c, const sbag_forest* f, const double* X, int64_t N, int32_t F,
+                               int32_t class_index, const double* weights, double* out) {
+  if (!c || !f || !X || !out || N < 0 || F <= 0) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  for (const HTree& t : f->trees)
+    for (int32_t g : t.sub)
+      if (g >= F) return fail(SBAG_EINVAL, "feature vector shorter than a subspace index");
+  ContribPlan P;
+  TRY(contrib_paths(f, class_index, weights, P));
+  if (N == 0) return SBAG_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  // rows are binned on the device against the forest's own thresholds, as in sbag_predict
+  std::vector<std::vector<double>> T(F);
+  for (const HTree& t : f->trees)
+    for (const sbag_node& n : t.nodes)
+      if (n.left >= 0) T[t.sub[n.feature]].push_back(n.threshold);
+  std::vector<int64_t> toff(F + 1, 0);
+  size_t max_thr = 0;
+  for (int g = 0; g < F; g++) {
+    std::sort(T[g].begin(), T[g].end());
+    T[g].erase(std::unique(T[g].begin(), T[g].end()), T[g].end());
+    toff[g + 1] = toff[g] + (int64_t)T[g].size();
+    max_thr = std::max(max_thr, T[g].size());
+  }
+  const int32_t Sq = (F + 15) / 16 * 16;
+  ContribRun R;
+  TRY(contrib_prepare(c, P, weights ? 0 : (int)f->trees.size(), 2, Sq, F, max_thr <= 65535,
+                      [&](int g, double thr) {
+                        return (int64_t)(std::lower_bound(T[g].begin(), T[g].end(), thr) - T[g].begin());
+                      }, R));
+  const int64_t batch = contrib_batch_rows(N, F);
+  double *d_out, *d_X, *d_T = nullptr;
+  int64_t* d_toff = nullptr;
+  uint16_t* d_codes = nullptr;
+  TRY(ws_typed(c, "pcout", (size_t)batch * (F + 1), &d_out));
+  TRY(ws_typed(c, "pX", (size_t)batch * F, &d_X));
+  if (R.tiled) {
+    std::vector<double> tv((size_t)std::max<int64_t>(toff[F], 1));
+    for (int g = 0; g < F; g++) std::copy(T[g].begin(), T[g].end(), tv.begin() + toff[g]);
+    TRY(ws_typed(c, "pq_thr", tv.size(), &d_T));
+    TRY(ws_typed(c, "pq_off", toff.size(), &d_toff));
+    TRY(h2d(c, d_T, tv.data(), tv.size()));
+    TRY(h2d(c, d_toff, toff.data(), toff.size()));
+    TRY(ws_typed(c, "pq_codes", (size_t)batch * Sq, &d_codes));
+  }
+  R.a.out = d_out;
+  for (int64_t r0 = 0; r0 < N; r0 += batch) {
+    const int64_t n = std::min(batch, N - r0);
+    HIP_TRY(hipMemcpyAsync(d_X, X + r0 * F, (size_t)n * F * 8, hipMemcpyHostToDevice, c->stream));
+    R.a.N = n;
+    if (R.tiled) {
+      launch_quantize(c->stream, d_X, n, F, d_T, d_toff, d_codes, Sq);
+      R.a.codes = d_codes;
+      launch_contrib_tiled(c->stream, R.a);
+    } else {
+      launch_contrib_walk(c->stream, d_X, nullptr, 1, nullptr, nullptr, F, R.a);
+    }
+    HIP_TRY(hipGetLastError());
+    TRY(d2h(c, out + r0 * (F + 1), d_out, (size_t)n * (F + 1)));
+  }
+  return SBAG_OK;
+}
+
+int sbag_predict_contributions_dataset(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds,
+                                       int32_t class_index, const double* weights, double* out) {
+  if (!c || !f || !ds || !out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(check_quant_dataset(c, f, ds));
+  ContribPlan P;
+  TRY(contrib_paths(f, class_index, weights, P));
+  if (ds->N == 0) return SBAG_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const int F = ds->F;
+  ContribRun R;
+  // TreePoint's `value <= threshold` in the dataset's code space (dict sorted ascending)
+  TRY(contrib_prepare(c, P, weights ? 0 : (int)f->trees.size(), ds->code_bytes, ds->S, F, ds->code_bytes != 4,
+                      [&](int g, double thr) {
+                        const std::vector<double>& d = ds->dict[g];
+                        return (int64_t)(std::upper_bound(d.begin(), d.end(), thr) - d.begin()) - 1;
+                      }, R));
+  const int64_t batch = contrib_batch_rows(ds->N, F);
+  double* d_out;
+  TRY(ws_typed(c, "pcout", (size_t)batch * (F + 1), &d_out));
+  R.a.out = d_out;
+  for (int64_t r0 = 0; r0 < ds->N; r0 += batch) {  // the rows stay resident; the results come down in batches
+    const int64_t n = std::min(batch, ds->N - r0);
+    const unsigned char* codes = (const unsigned char*)ds->d_codes + (size_t)r0 * ds->S * ds->code_bytes;
+    R.a.N = n;
+    R.a.codes = codes;
+    if (R.tiled)
+      launch_contrib_tiled(c->stream, R.a);
+    else
+      launch_contrib_walk(c->stream, nullptr, codes, ds->code_bytes, ds->d_dict, ds->d_dict_off, ds->S, R.a);
+    HIP_TRY(hipGetLastError());
+    TRY(d2h(c, out + r0 * (F + 1), d_out, (size_t)n * (F + 1)));
+  }
+  return SBAG_OK;
+}
+
 int sbag_predict_raw(sbag_ctx* c, const sbag_forest* f, const double* X, int64_t N, int32_t F,
                      int32_t kind, int32_t num_classes, double* raw_out) {
   if (!c || !f || !X || !raw_out || N < 0 || F <= 0) return fail(SBAG_EINVAL, "bad arguments");

@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "sbag_contrib_plan.h"
+
 namespace sbag {
 
 // Workgroup barrier with the waits spelled out.  gfx950 has the back-off barrier, so the
@@ -511,6 +513,29 @@ struct PdFoldArgs {
 void launch_pd_fold(hipStream_t st, const PdFoldArgs& a);
 // zeroes n 64-bit words
 void launch_pd_zero(hipStream_t st, unsigned long long* p, int64_t n);
+// ---- per-row feature contributions (sbag_contrib.hip) over the packed path table of
+// sbag_contrib_plan.h: out[row][g] by sbag.h's rule (sbag_predict_contributions).
+struct ContribArgs {
+  const void* codes;          // k_contrib_tiled: [N][S] u8 / u16
+  int32_t code_bytes, S;
+  int64_t N;
+  const ContribLeaf* leaves;  // [nleaves], forest order, pre-order within a tree
+  const void* elems;          // ContribElem (tiled) / ContribElemF (walk)
+  int64_t nleaves;
+  const double* q;            // Q table [(M + 2)][(M + 2)] (contrib_q_count)
+  int32_t M;                  // the forest's largest m
+  int32_t F;
+  int32_t rows, lanes;        // k_contrib_tiled: rows of a tile, lanes of a group (8 / 16)
+  int32_t trees;              // the divisor of the mean; 0 with weights: no division
+  double bias;                // column F of every row, computed on the host
+  double* out;                // [N][F + 1], row-major
+};
+// k_contrib_tiled: LDS = contrib_lds(rows, S * code_bytes + 4, F, M)
+void launch_contrib_tiled(hipStream_t st, const ContribArgs& a);
+// k_contrib_walk: one thread per row (X fp64 rows [N][F], or codes at stride S + dictionaries as
+// launch_predict)
+void launch_contrib_walk(hipStream_t st, const double* X, const void* codes, int code_bytes,
+                         const double* dict, const int64_t* dict_off, int32_t S, const ContribArgs& a);
 // ---- out-of-bag predictions under permuted features (sbag_oobperm.hip): slot k of a
 // feature batch is sbag_predict_oob with feature feat[k] of row r taken from row src[k][r].
 // Between learner batches a slot's state lives in global memory as the baseline's does:

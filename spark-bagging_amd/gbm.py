@@ -33,7 +33,7 @@ from . import _native as nat
 from . import persistence as sp
 from .libsvm import is_sparse
 from .ml import (DecisionTreeModel, DecisionTreeRegressor, Frame, Params, _DecisionTreeEstimator,
-                 _in_range01, java_string_hash, partial_dependence)
+                 _in_range01, java_string_hash, partial_dependence, predict_contributions)
 
 SUPPORTED_LOSSES = ("squared", "absolute", "huber", "quantile")
 DOUBLE_MAX = np.finfo(np.float64).max
@@ -186,6 +186,14 @@ class GBMRegressionModel(_GBMParams):
         grid, pd = partial_dependence(self.native_forest(), dataset, feature, grid, numPoints, nat.PD_MEAN,
                                       weights=self.weights, perTree=perTree, device=device)
         return (grid, (pd[0] + self.const, pd[1])) if perTree else (grid, pd + self.const)
+
+    def predictContributions(self, dataset, device=0):
+        """fp64 [N, F + 1]: each feature's contribution to each row's prediction (path-dependent
+        TreeSHAP, the in-order weighted sum over the boosters, made on the device), and the
+        model's expected value, const included, in the last column."""
+        out = predict_contributions(self, nat.IMPURITY_VARIANCE, dataset, weights=self.weights, device=device)
+        out[:, -1] += self.const
+        return out
 
     # ---- persistence: GBMRegressionModelWriter (GBMRegressor.scala:535-559)
     def save(self, path):

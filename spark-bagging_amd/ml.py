@@ -900,6 +900,35 @@ def partial_dependence(forest, dataset, feature, grid, numPoints, kind, weights=
     return grid, nat.partial_dependence(ctx, forest, X, feature, grid, kind, weights=weights, per_tree=perTree)
 
 
+def predict_contributions(model, impurity, dataset, class_index=-1, weights=None, device=0):
+    """fp64 [N, F + 1] per-row feature contributions (TreeSHAP) of `model`'s trees and the bias
+    (sbag_predict_contributions(_dataset)).  `dataset` as in transform; a DeviceDataset stays
+    resident and is served by its own context (`device` is for host rows).  The covers are the
+    trees' impurity stats, so the call builds a native forest that carries them from the model's
+    trees as they are now and frees it when it is done: nothing is kept on the model, and
+    native_forest(), save and pickling are as they were."""
+    if not all(m.stats is not None and np.ndim(m.stats) == 2 and np.shape(m.stats)[0] == len(m.nodes)
+               and np.shape(m.stats)[1] > 0 for m in model.models):
+        raise nat.IllegalArgumentException(nat.SBAG_EINVAL, "contributions need every tree's impurity stats")
+    # a variance tree's cover is its first stat; its sum of labels may be negative, which
+    # sbag_forest_create_stats refuses, and is not needed
+    width = None if impurity == nat.IMPURITY_GINI else 1
+    forest = nat.NativeForest.from_trees([m.nodes for m in model.models], model.subspaces, impurity,
+                                         stats=[np.asarray(m.stats)[:, :width] for m in model.models])
+    try:
+        if isinstance(dataset, nat.DeviceDataset):
+            return nat.predict_contributions_dataset(dataset.ctx, forest, dataset, class_index, weights)
+        X = dataset.features if isinstance(dataset, Frame) else dataset
+        if is_sparse(X):
+            X = X.toarray() if hasattr(X, "toarray") else X.to_dense()
+        X = np.asarray(X, np.float64)
+        if X.ndim == 1:
+            X = X[None, :]
+        return nat.predict_contributions(nat.default_context(device), forest, X, class_index, weights)
+    finally:
+        forest.free()
+
+
 class BaggingRegressionModel(_BaggingModel):
     _agg = nat.AGG_MEAN
     _spark_class = "org.apache.spark.ml.regression.BaggingRegressionModel"
@@ -934,6 +963,12 @@ class BaggingRegressionModel(_BaggingModel):
         one walk per row and tree.  perTree: pd is (pd [G], tree_pd [trees, G])."""
         return partial_dependence(self.native_forest(), dataset, feature, grid, numPoints, nat.PD_MEAN,
                                   perTree=perTree, device=device)
+
+    def predictContributions(self, dataset, device=0):
+        """fp64 [N, F + 1]: how much each feature moved each row's prediction (path-dependent
+        TreeSHAP, the mean over the trees), and the ensemble's expected value in the last column.
+        A row sums to its prediction up to rounding."""
+        return predict_contributions(self, nat.IMPURITY_VARIANCE, dataset, device=device)
 
     def predictInterval(self, dataset, coverage=0.9, device=0):
         """(lower, upper): the ensemble's quantiles at (1 - coverage) / 2 and (1 + coverage) / 2."""
@@ -1076,6 +1111,12 @@ class BaggingClassificationModel(_BaggingModel):
         else:
             y = dataset.label if isinstance(dataset, Frame) else dataset[1]
         return oob_log_loss(proba, n_oob, y)
+
+    def predictContributions(self, dataset, classIndex, device=0):
+        """fp64 [N, F + 1]: each feature's contribution to class `classIndex`'s soft-vote
+        probability of each row (path-dependent TreeSHAP of the trees' leaf class fractions, the
+        mean over the trees), and its expected value in the last column."""
+        return predict_contributions(self, nat.IMPURITY_GINI, dataset, class_index=int(classIndex), device=device)
 
     def partialDependence(self, dataset, feature, grid=None, numPoints=32, device=0):
         """(grid, pd [G, numClasses]): the fraction of the (row, tree) votes each class gets with
