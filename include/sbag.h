@@ -635,6 +635,63 @@ int sbag_predict_contributions(sbag_ctx* ctx, const sbag_forest* f, const double
                                double* out /* host [num_rows x (num_features + 1)], row-major */);
 int sbag_predict_contributions_dataset(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* ds,
                                        int32_t class_index, const double* weights, double* out);
+/* ---- forest proximities (Breiman's proximity matrix, randomForest's proximity = TRUE and
+ * outlier(); sklearn's apply is the first step): in how many trees two rows reach the same leaf.
+ *   Leaf code.  The leaf code of (row r, tree t) is the number of leaf nodes that come before
+ *               the reached leaf in tree t's pre-order node array.
+ *   Routing.    The tree's subspace and the `<=` rule of sbag_predict: left iff value <=
+ *               threshold, so NaN goes right and -0.0 equals +0.0.
+ *   Pair count. cnt(i, j) = #{t : code_t(q_i) == code_t(r_j)} over every tree of the forest, an
+ *               integer in [0, trees].  The proximity is cnt / trees; the caller divides, nothing
+ *               fp64 happens on the device and no order has to be fixed: every result is one
+ *               well-defined integer.
+ * sbag_predict_leaves(_dataset): out is host int32 [num_rows x trees], row-major, the node id
+ *   (sbag_node.id, the index in the tree's node array) of the leaf each row reaches in each tree.
+ * sbag_proximity(_dataset): out is host uint16 [nq x nr], row-major, cnt(i, j) of query row i
+ *   and reference row j.  The full rectangle is computed, also when both row sets are the same
+ *   (the two datasets may be one object).  The query rows go in batches: neither the device
+ *   buffers nor the pinned staging buffers grow with nq.
+ * sbag_proximity_moments(_dataset): ref_group is host int32 [nr] with values in [0, num_groups),
+ *   num_groups in [1, 16]; out is host uint64 [nq x num_groups x 2], row-major:
+ *     out[i][g][0] = sum over the j with ref_group[j] == g of cnt(i, j)
+ *     out[i][g][1] = sum over the j with ref_group[j] == g of cnt(i, j)^2
+ *   A group without rows gives zeros.  The pair matrix never leaves the kernel.  The sums are
+ *   exact: cnt <= 65 535 and nr < 2^31, so a sum of squares is below 2^63, and integer addition
+ *   makes them independent of the order of accumulation.
+ * nq == 0 and nr == 0 are SBAG_OK (moments of no reference rows are zeros).  A forest of either
+ * impurity is accepted: a leaf is a leaf.
+ * SBAG_EINVAL (nothing written, the context stays usable): a null argument, a group id outside
+ * [0, num_groups), num_groups outside [1, 16], row sets whose feature counts differ, and the
+ * argument errors of sbag_predict / sbag_predict_dataset (a subspace past the features, a
+ * dataset on another device).  SBAG_EUNSUPPORTED: more than 65 535 trees, a tree with more than
+ * 65 536 leaves, 2^31 or more reference rows.
+ * Stage A writes one signature per row: the row's leaf codes, u8 when no tree has more than 256
+ * leaves (code 0xFF is then a real leaf) and u16 otherwise, zero padded to a multiple of 16
+ * bytes on both sides, so that cnt = trees - #{differing codes} needs no mask.  u8 / u16 feature
+ * codes whose row tile (512, 256, 128 or 64 rows), signatures and a forest chunk fit the LDS go
+ * through the tiled walk (host rows are binned against the forest's thresholds first, in row
+ * batches as in sbag_predict); u32 codes, larger trees, a feature of host rows with more than
+ * 65 535 thresholds and every call under SBAG_PROX_FORCE_FALLBACK=1 (read on every call) walk
+ * global memory, one thread per row: the same signatures.  Stage B is one tiled all-pairs
+ * kernel over the two signature matrices (sbag_proximity_tile: the pairs of one block), a packed
+ * compare in the place of a multiply-add.                                                    */
+int sbag_proximity_tile(int32_t* block_rows, int32_t* block_cols);
+int sbag_predict_leaves(sbag_ctx* ctx, const sbag_forest* f, const double* X, int64_t num_rows,
+                        int32_t num_features, int32_t* out /* host [num_rows x trees] */);
+int sbag_predict_leaves_dataset(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* ds,
+                                int32_t* out);
+int sbag_proximity(sbag_ctx* ctx, const sbag_forest* f, const double* Xq, int64_t nq,
+                   int32_t num_features_q, const double* Xr, int64_t nr, int32_t num_features_r,
+                   uint16_t* out /* host [nq x nr] */);
+int sbag_proximity_dataset(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* queries,
+                           const sbag_dataset* references, uint16_t* out);
+int sbag_proximity_moments(sbag_ctx* ctx, const sbag_forest* f, const double* Xq, int64_t nq,
+                           int32_t num_features_q, const double* Xr, int64_t nr,
+                           int32_t num_features_r, const int32_t* ref_group /* host [nr] */,
+                           int32_t num_groups, uint64_t* out /* host [nq x num_groups x 2] */);
+int sbag_proximity_moments_dataset(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* queries,
+                                   const sbag_dataset* references, const int32_t* ref_group,
+                                   int32_t num_groups, uint64_t* out);
 /* ---- Stacking: the level-1 dataset and the two-level transform -----------------------------
  * StackingRegressor.train (ml/regression/StackingRegressor.scala:163-171) and
  * StackingClassifier.train (ml/classification/StackingClassifier.scala:164-172) map every

@@ -41,6 +41,8 @@ EXPORTED = [
     "sbag_predict_quantiles", "sbag_predict_quantiles_dataset", "sbag_predict_oob_quantiles",
     "sbag_partial_dependence", "sbag_partial_dependence_dataset",
     "sbag_predict_contributions", "sbag_predict_contributions_dataset",
+    "sbag_proximity_tile", "sbag_predict_leaves", "sbag_predict_leaves_dataset",
+    "sbag_proximity", "sbag_proximity_dataset", "sbag_proximity_moments", "sbag_proximity_moments_dataset",
 ]
 
 
@@ -188,6 +190,13 @@ def lib():
             "sbag_partial_dependence_dataset": [P, P, P, i32, P, i32, i32, i32, P, P, P],
             "sbag_predict_contributions": [P, P, P, i64, i32, i32, P, P],
             "sbag_predict_contributions_dataset": [P, P, P, i32, P, P],
+            "sbag_proximity_tile": [P, P],
+            "sbag_predict_leaves": [P, P, P, i64, i32, P],
+            "sbag_predict_leaves_dataset": [P, P, P, P],
+            "sbag_proximity": [P, P, P, i64, i32, P, i64, i32, P],
+            "sbag_proximity_dataset": [P, P, P, P, P],
+            "sbag_proximity_moments": [P, P, P, i64, i32, P, i64, i32, P, i32, P],
+            "sbag_proximity_moments_dataset": [P, P, P, P, P, i32, P],
             "sbag_forest_timing": [P, ctypes.POINTER(Timing)],
             "sbag_predict": [P, P, P, i64, i32, i32, P, P],
             "sbag_predict_dataset": [P, P, P, i32, P],
@@ -866,6 +875,76 @@ def predict_contributions_dataset(ctx, forest, dataset, class_index=-1, weights=
     out = np.zeros((n, F + 1), np.float64)
     check(lib().sbag_predict_contributions_dataset(ctx.handle, forest.handle, dataset.handle, int(class_index),
                                                    ptr(w), ptr(out)))
+    return out
+
+
+def proximity_tile():
+    """(block rows, block columns) of the pair kernel's tile (sbag_prox_plan.h)."""
+    bm, bn = ctypes.c_int32(), ctypes.c_int32()
+    check(lib().sbag_proximity_tile(ctypes.byref(bm), ctypes.byref(bn)))
+    return bm.value, bn.value
+
+
+def predict_leaves(ctx, forest, X):
+    """The node id of the leaf every host row reaches in every tree (sbag_predict_leaves,
+    sklearn's apply): int32 [N, trees]."""
+    X = np.ascontiguousarray(X, np.float64)
+    out = np.zeros((X.shape[0], len(forest)), np.int32)
+    check(lib().sbag_predict_leaves(ctx.handle, forest.handle, ptr(X), X.shape[0], X.shape[1], ptr(out)))
+    return out
+
+
+def predict_leaves_dataset(ctx, forest, dataset):
+    """predict_leaves over a device dataset (sbag_predict_leaves_dataset)."""
+    out = np.zeros((dataset.shape[0], len(forest)), np.int32)
+    check(lib().sbag_predict_leaves_dataset(ctx.handle, forest.handle, dataset.handle, ptr(out)))
+    return out
+
+
+def proximity(ctx, forest, Xq, Xr):
+    """Pair counts of host rows (sbag_proximity): uint16 [nq, nr], in how many trees query row
+    i and reference row j reach the same leaf."""
+    Xq = np.ascontiguousarray(Xq, np.float64)
+    Xr = np.ascontiguousarray(Xr, np.float64)
+    out = np.zeros((Xq.shape[0], Xr.shape[0]), np.uint16)
+    check(lib().sbag_proximity(ctx.handle, forest.handle, ptr(Xq), Xq.shape[0], Xq.shape[1], ptr(Xr),
+                               Xr.shape[0], Xr.shape[1], ptr(out)))
+    return out
+
+
+def proximity_dataset(ctx, forest, queries, references):
+    """proximity over two device datasets, which may be the same one (sbag_proximity_dataset)."""
+    out = np.zeros((queries.shape[0], references.shape[0]), np.uint16)
+    check(lib().sbag_proximity_dataset(ctx.handle, forest.handle, queries.handle, references.handle, ptr(out)))
+    return out
+
+
+def _groups(groups, nr):
+    g = np.ascontiguousarray(groups, np.int32).reshape(-1)
+    if len(g) != nr:
+        raise IllegalArgumentException(SBAG_EINVAL, f"{len(g)} group ids for {nr} reference rows")
+    return g
+
+
+def proximity_moments(ctx, forest, Xq, Xr, groups, num_groups):
+    """Per query row and group of reference rows the sum of the pair counts and of their
+    squares (sbag_proximity_moments): uint64 [nq, num_groups, 2]; the pair matrix stays on the
+    device."""
+    Xq = np.ascontiguousarray(Xq, np.float64)
+    Xr = np.ascontiguousarray(Xr, np.float64)
+    g = _groups(groups, Xr.shape[0])
+    out = np.zeros((Xq.shape[0], max(int(num_groups), 0), 2), np.uint64)
+    check(lib().sbag_proximity_moments(ctx.handle, forest.handle, ptr(Xq), Xq.shape[0], Xq.shape[1], ptr(Xr),
+                                       Xr.shape[0], Xr.shape[1], ptr(g), int(num_groups), ptr(out)))
+    return out
+
+
+def proximity_moments_dataset(ctx, forest, queries, references, groups, num_groups):
+    """proximity_moments over two device datasets (sbag_proximity_moments_dataset)."""
+    g = _groups(groups, references.shape[0])
+    out = np.zeros((queries.shape[0], max(int(num_groups), 0), 2), np.uint64)
+    check(lib().sbag_proximity_moments_dataset(ctx.handle, forest.handle, queries.handle, references.handle,
+                                               ptr(g), int(num_groups), ptr(out)))
     return out
 
 

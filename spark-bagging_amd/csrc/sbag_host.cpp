@@ -36,6 +36,7 @@
 #include "sbag_internal.h"
 #include "sbag_mfma_plan.h"
 #include "sbag_pd_plan.h"
+#include "sbag_prox_plan.h"
 #include "sbag_spread_plan.h"
 #include "sbag_stack_plan.h"
 
@@ -5965,6 +5966,446 @@ int sbag_predict_oob_quantiles(sbag_ctx* c, const sbag_forest* f, const sbag_dat
   TRY(quant_dataset(c, f, ds, probs, num_probs, R, out));
   if (n_oob_out && N > 0) TRY(d2h(c, n_oob_out, R.q.n_oob, (size_t)N));
   return SBAG_OK;
+}
+
+}  // extern "C"
+
+// ---- forest proximities (sbag_prox.hip).  Stage A turns rows into leaf signatures: through
+// k_leaf_tiled when the codes are u8 / u16, prox_tile_rows finds a row tile and plan_tiled holds
+// the forest beside the tile's signatures, and SBAG_PROX_FORCE_FALLBACK is not set (read on
+// every call); else through k_leaf_walk.  Stage B (k_prox_tiled) counts the pairs of two
+// signature matrices.  The reference rows' signatures stay on the device for the whole call, the
+// query rows go in batches (sbag_prox_plan.h), so nothing grows with the query count.
+struct ProxRows {  // one row set: host rows, or a resident dataset
+  const double* X = nullptr;
+  const sbag_dataset* ds = nullptr;
+  int64_t N = 0;
+  int32_t F = 0;
+};
+
+struct ProxShape {
+  int L = 0, code_bytes = 1, tpad = 16;
+};
+
+static int check_prox_rows(sbag_ctx* c, const sbag_forest* f, const ProxRows& r) {
+  if (r.ds) return check_quant_dataset(c, f, r.ds);
+  if (r.N < 0 || r.F <= 0) return fail(SBAG_EINVAL, "bad arguments");
+  for (const HTree& t : f->trees)
+    for (int32_t g : t.sub)
+      if (g >= r.F) return fail(SBAG_EINVAL, "feature vector shorter than a subspace index");
+  return SBAG_OK;
+}
+
+static int prox_shape(const sbag_forest* f, ProxShape& sh) {
+  sh.L = (int)f->trees.size();
+  if (sh.L > kProxMaxTrees)
+    return fail(SBAG_EUNSUPPORTED, "proximities over " + std::to_string(sh.L) + " trees (limit " +
+                                       std::to_string(kProxMaxTrees) + ")");
+  int64_t max_leaves = 1;
+  for (const HTree& t : f->trees) {
+    int64_t n = 0;
+    for (const sbag_node& k : t.nodes) n += k.left < 0 ? 1 : 0;
+    max_leaves = std::max(max_leaves, n);
+  }
+  if (max_leaves > kProxMaxLeaves)
+    return fail(SBAG_EUNSUPPORTED, "a tree with " + std::to_string(max_leaves) + " leaves (limit " +
+                                       std::to_string(kProxMaxLeaves) + ")");
+  sh.code_bytes = prox_code_bytes(max_leaves);
+  sh.tpad = prox_tpad(sh.L, sh.code_bytes);
+  return SBAG_OK;
+}
+
+struct LeafRun {
+  bool tiled = false;
+  PredictArgs pa{};                // tiled: the uploaded plan (codes / N set per launch)
+  LeafArgs la{};
+  const DevNode* nodes = nullptr;  // general path
+  const int64_t* off = nullptr;
+  double* d_T = nullptr;           // host rows, tiled: the forest's thresholds, as sbag_predict's
+  int64_t* d_toff = nullptr;
+  int32_t Sq = 0;
+};
+
+// the plan of stage A over one row set, uploaded
+static int leaf_prepare(sbag_ctx* c, const sbag_forest* f, const ProxRows& rows, const ProxShape& sh, LeafRun& R) {
+  const int L = sh.L;
+  R.la.tpad = sh.tpad;
+  R.la.code_bytes = sh.code_bytes;
+  const char* ffb = getenv("SBAG_PROX_FORCE_FALLBACK");
+  bool may_tile = !(ffb && atoi(ffb) != 0);
+  const int F = rows.ds ? rows.ds->F : rows.F;
+  std::vector<std::vector<double>> T;
+  std::vector<int64_t> toff;
+  if (rows.ds) {
+    R.pa.code_bytes = rows.ds->code_bytes;
+    R.pa.S = rows.ds->S;
+    may_tile = may_tile && rows.ds->code_bytes != 4;
+  } else {  // rows are binned on the device against the forest's own thresholds, as in sbag_predict
+    T.resize(F);
+    for (const HTree& t : f->trees)
+      for (const sbag_node& n : t.nodes)
+        if (n.left >= 0) T[t.sub[n.feature]].push_back(n.threshold);
+    toff.assign(F + 1, 0);
+    size_t max_thr = 0;
+    for (int g = 0; g < F; g++) {
+      std::sort(T[g].begin(), T[g].end());
+      T[g].erase(std::unique(T[g].begin(), T[g].end()), T[g].end());
+      toff[g + 1] = toff[g] + (int64_t)T[g].size();
+      max_thr = std::max(max_thr, T[g].size());
+    }
+    R.Sq = (F + 15) / 16 * 16;
+    R.pa.code_bytes = 2;
+    R.pa.S = R.Sq;
+    may_tile = may_tile && max_thr <= 65535;
+  }
+  R.pa.agg = kAggMean;  // predict_tiled_lds: the row tile and the chunk; the signatures are extra
+  const int Rt = may_tile ? prox_tile_rows(R.pa.S * R.pa.code_bytes + 4, sh.tpad) : 0;
+  TiledPlan P;
+  if (Rt > 0) {
+    if (rows.ds)  // TreePoint's `value <= threshold` in the dataset's code space (dict sorted ascending)
+      R.tiled = plan_tiled(f, R.pa, F, [&](int g, double thr) {
+        const std::vector<double>& d = rows.ds->dict[g];
+        return (int64_t)(std::upper_bound(d.begin(), d.end(), thr) - d.begin()) - 1;
+      }, P, prox_sig_lds(sh.tpad, Rt), 0, Rt);
+    else
+      R.tiled = plan_tiled(f, R.pa, F, [&](int g, double thr) {
+        return (int64_t)(std::lower_bound(T[g].begin(), T[g].end(), thr) - T[g].begin());
+      }, P, prox_sig_lds(sh.tpad, Rt), 0, Rt);
+  }
+  if (!R.tiled) return upload_forest(c, f, &R.nodes, &R.off);
+  R.la.R = Rt;
+  for (int t = 0; t < L; t++) {  // a leaf node carries its code: the leaves before it in node order
+    const HTree& h = f->trees[t];
+    std::vector<int32_t> code(h.nodes.size(), 0);
+    int32_t leaves = 0;
+    for (size_t k = 0; k < h.nodes.size(); k++)
+      if (h.nodes[k].left < 0) code[k] = leaves++;
+    std::vector<int> order{0};  // plan_tiled's breadth-first order
+    for (size_t k = 0; k < order.size(); k++) {
+      const sbag_node& n = h.nodes[order[k]];
+      if (n.left >= 0) {
+        order.push_back(n.left);
+        order.push_back(n.right);
+      }
+    }
+    for (size_t k = 0; k < order.size(); k++)
+      if (P.pn[P.tn[t] + k].a & 0x80000000u) P.pn[P.tn[t] + k].a = 0x80000000u | (uint32_t)code[order[k]];
+  }
+  TRY(upload_plan(c, P, R.pa));
+  if (!rows.ds) {
+    std::vector<double> tv((size_t)std::max<int64_t>(toff[F], 1));
+    for (int g = 0; g < F; g++) std::copy(T[g].begin(), T[g].end(), tv.begin() + toff[g]);
+    TRY(ws_typed(c, "pq_thr", tv.size(), &R.d_T));
+    TRY(ws_typed(c, "pq_off", toff.size(), &R.d_toff));
+    TRY(h2d(c, R.d_T, tv.data(), tv.size()));
+    TRY(h2d(c, R.d_toff, toff.data(), toff.size()));
+  }
+  return SBAG_OK;
+}
+
+// the signatures of rows [r0, r0 + n) of a row set into sig [n][tpad]
+static int leaf_run(sbag_ctx* c, const sbag_forest* f, LeafRun& R, const ProxRows& rows, int64_t r0, int64_t n,
+                    unsigned char* sig) {
+  const int L = (int)f->trees.size();
+  LeafArgs la = R.la;
+  la.sig = sig;
+  if (rows.ds) {
+    const sbag_dataset* ds = rows.ds;
+    const unsigned char* codes = (const unsigned char*)ds->d_codes + (size_t)r0 * ds->S * ds->code_bytes;
+    if (R.tiled) {
+      R.pa.codes = codes;
+      R.pa.N = n;
+      launch_leaf_tiled(c->stream, R.pa, la);
+    } else {
+      launch_leaf_walk(c->stream, nullptr, codes, ds->code_bytes, ds->d_dict, ds->d_dict_off, n, ds->F, ds->S,
+                       R.nodes, R.off, L, la);
+    }
+    HIP_TRY(hipGetLastError());
+    return SBAG_OK;
+  }
+  const int F = rows.F;
+  int64_t batch = std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)2 << 30) / (8 * (int64_t)F)));
+  if (const char* e = getenv("SBAG_PREDICT_BATCH_ROWS")) batch = std::max<int64_t>(1, std::min<int64_t>(batch, atoll(e)));
+  double* d_X;
+  uint16_t* d_codes = nullptr;
+  TRY(ws_typed(c, "pX", (size_t)batch * F, &d_X));
+  if (R.tiled) TRY(ws_typed(c, "pq_codes", (size_t)batch * R.Sq, &d_codes));
+  for (int64_t b0 = 0; b0 < n; b0 += batch) {
+    const int64_t nb = std::min(batch, n - b0);
+    HIP_TRY(hipMemcpyAsync(d_X, rows.X + (r0 + b0) * F, (size_t)nb * F * 8, hipMemcpyHostToDevice, c->stream));
+    la.sig = sig + b0 * la.tpad;
+    if (R.tiled) {
+      launch_quantize(c->stream, d_X, nb, F, R.d_T, R.d_toff, d_codes, R.Sq);
+      R.pa.codes = d_codes;
+      R.pa.N = nb;
+      launch_leaf_tiled(c->stream, R.pa, la);
+    } else {
+      launch_leaf_walk(c->stream, d_X, nullptr, 1, nullptr, nullptr, nb, F, F, R.nodes, R.off, L, la);
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  return SBAG_OK;
+}
+
+// sbag_predict_leaves(_dataset): stage A, then a code's node id from the forest's table
+static int leaves_run(sbag_ctx* c, const sbag_forest* f, const ProxRows& rows, int32_t* out) {
+  ProxShape sh;
+  TRY(prox_shape(f, sh));
+  const int64_t N = rows.ds ? rows.ds->N : rows.N;
+  if (N == 0 || sh.L == 0) return SBAG_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  LeafRun R;
+  TRY(leaf_prepare(c, f, rows, sh, R));
+  std::vector<int32_t> node_of;
+  std::vector<int64_t> lo;
+  for (const HTree& t : f->trees) {
+    lo.push_back((int64_t)node_of.size());
+    for (size_t k = 0; k < t.nodes.size(); k++)
+      if (t.nodes[k].left < 0) node_of.push_back((int32_t)k);
+  }
+  int32_t *d_node_of, *d_ids;
+  int64_t* d_lo;
+  unsigned char* d_sig;
+  TRY(ws_typed(c, "px_nodeof", node_of.size(), &d_node_of));
+  TRY(ws_typed(c, "px_leafoff", lo.size(), &d_lo));
+  TRY(h2d(c, d_node_of, node_of.data(), node_of.size()));
+  TRY(h2d(c, d_lo, lo.data(), lo.size()));
+  const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(N, ((int64_t)256 << 20) / (4 * (int64_t)sh.L + sh.tpad)));
+  TRY(ws_typed(c, "px_sigq", (size_t)batch * sh.tpad, &d_sig));
+  TRY(ws_typed(c, "px_ids", (size_t)batch * sh.L, &d_ids));
+  for (int64_t r0 = 0; r0 < N; r0 += batch) {
+    const int64_t n = std::min(batch, N - r0);
+    TRY(leaf_run(c, f, R, rows, r0, n, d_sig));
+    LeafArgs la = R.la;
+    la.sig = d_sig;
+    launch_leaf_ids(c->stream, la, n, sh.L, d_node_of, d_lo, d_ids);
+    HIP_TRY(hipGetLastError());
+    TRY(d2h(c, out + r0 * sh.L, d_ids, (size_t)n * sh.L));
+  }
+  return SBAG_OK;
+}
+
+// counts mode's second stream: a batch's counts come down through pinned memory while the next
+// batch runs.  Everything here lives for one call and does not grow with the query count.
+struct ProxPipe {
+  hipStream_t copy = nullptr;
+  hipEvent_t done[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr};
+  uint16_t* pin[2] = {nullptr, nullptr};
+  ~ProxPipe() {
+    if (copy) (void)hipStreamSynchronize(copy);
+    for (int i = 0; i < 2; i++) {
+      if (done[i]) (void)hipEventDestroy(done[i]);
+      if (copied[i]) (void)hipEventDestroy(copied[i]);
+      if (pin[i]) (void)hipHostFree(pin[i]);
+    }
+    if (copy) (void)hipStreamDestroy(copy);
+  }
+};
+
+// out_cnt: u16 [nq][nr] pair counts; out_mom (with ref_group / G): u64 [nq][G][2]
+static int prox_run(sbag_ctx* c, const sbag_forest* f, const ProxRows& q, const ProxRows& r,
+                    const int32_t* ref_group, int G, uint16_t* out_cnt, uint64_t* out_mom) {
+  ProxShape sh;
+  TRY(prox_shape(f, sh));
+  const int64_t nq = q.ds ? q.ds->N : q.N, nr = r.ds ? r.ds->N : r.N;
+  if (nr > INT32_MAX) return fail(SBAG_EUNSUPPORTED, "more than 2^31 - 1 reference rows");
+  if (nq == 0) return SBAG_OK;
+  if (nr == 0) {
+    if (out_mom) memset(out_mom, 0, (size_t)nq * G * 16);
+    return SBAG_OK;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  ProxArgs pa{};
+  pa.nr = nr;
+  pa.tpad = sh.tpad;
+  pa.code_bytes = sh.code_bytes;
+  pa.L = sh.L;
+  pa.G = G;
+  unsigned char* d_sigr;
+  TRY(ws_typed(c, "px_sigr", (size_t)nr * sh.tpad, &d_sigr));
+  {
+    LeafRun R;
+    TRY(leaf_prepare(c, f, r, sh, R));
+    TRY(leaf_run(c, f, R, r, 0, nr, d_sigr));
+  }
+  pa.sigr = d_sigr;
+  if (out_mom) {  // the reference rows in group order, no column block spanning two groups
+    std::vector<int64_t> perm;
+    std::vector<ProxColBlock> blocks;
+    prox_group_blocks(ref_group, nr, G, perm, blocks);
+    int64_t* d_perm;
+    ProxColBlock* d_blocks;
+    unsigned char* d_sigg;
+    TRY(ws_typed(c, "px_perm", perm.size(), &d_perm));
+    TRY(ws_typed(c, "px_blocks", blocks.size(), &d_blocks));
+    TRY(ws_typed(c, "px_sigg", (size_t)nr * sh.tpad, &d_sigg));
+    TRY(h2d(c, d_perm, perm.data(), perm.size()));
+    TRY(h2d(c, d_blocks, blocks.data(), blocks.size()));
+    launch_sig_gather(c->stream, d_sigr, d_perm, nr, sh.tpad, d_sigg);
+    HIP_TRY(hipGetLastError());
+    pa.sigr = d_sigg;
+    pa.blocks = d_blocks;
+    pa.nblocks = (int32_t)blocks.size();
+  }
+  LeafRun Q;
+  TRY(leaf_prepare(c, f, q, sh, Q));
+  const int64_t batch = std::min<int64_t>(out_mom ? prox_batch_moments(sh.tpad) : prox_batch_counts(nr, sh.tpad),
+                                          (nq + kProxBM - 1) / kProxBM * kProxBM);
+  unsigned char* d_sigq;
+  TRY(ws_typed(c, "px_sigq", (size_t)batch * sh.tpad, &d_sigq));
+  pa.sigq = d_sigq;
+  if (out_mom) {
+    unsigned long long* d_mom;
+    TRY(ws_typed(c, "px_mom", (size_t)batch * G * 2, &d_mom));
+    pa.moments = d_mom;
+    for (int64_t q0 = 0; q0 < nq; q0 += batch) {
+      const int64_t n = std::min(batch, nq - q0);
+      TRY(leaf_run(c, f, Q, q, q0, n, d_sigq));
+      HIP_TRY(hipMemsetAsync(d_mom, 0, (size_t)n * G * 16, c->stream));
+      pa.nq = n;
+      // enough blocks to fill the device, as few atomics a row as that allows
+      const int64_t row_blocks = (n + kProxBM - 1) / kProxBM;
+      const int64_t xs = std::max<int64_t>(1, std::min<int64_t>(pa.nblocks, (2048 + row_blocks - 1) / row_blocks));
+      pa.run = (int32_t)((pa.nblocks + xs - 1) / xs);
+      launch_prox_tiled(c->stream, pa);
+      HIP_TRY(hipGetLastError());
+      TRY(d2h(c, (unsigned long long*)out_mom + q0 * G * 2, d_mom, (size_t)n * G * 2));
+    }
+    return SBAG_OK;
+  }
+  ProxPipe pp;
+  uint16_t* d_cnt[2];
+  TRY(ws_typed(c, "px_cnt0", (size_t)batch * nr, &d_cnt[0]));
+  TRY(ws_typed(c, "px_cnt1", (size_t)batch * nr, &d_cnt[1]));
+  HIP_TRY(hipStreamCreateWithFlags(&pp.copy, hipStreamNonBlocking));
+  for (int i = 0; i < 2; i++) {
+    HIP_TRY(hipEventCreateWithFlags(&pp.done[i], hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&pp.copied[i], hipEventDisableTiming));
+    HIP_TRY(hipHostMalloc((void**)&pp.pin[i], (size_t)batch * nr * 2, hipHostMallocDefault));
+  }
+  int64_t prev_q0 = 0, prev_n = 0;
+  int b = 0;
+  for (int64_t q0 = 0; q0 < nq; q0 += batch, b++) {
+    const int s = b & 1;
+    const int64_t n = std::min(batch, nq - q0);
+    TRY(leaf_run(c, f, Q, q, q0, n, d_sigq));
+    if (b >= 2) HIP_TRY(hipStreamWaitEvent(c->stream, pp.copied[s], 0));  // the buffer's last copy is done
+    pa.nq = n;
+    pa.counts = d_cnt[s];
+    launch_prox_tiled(c->stream, pa);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(pp.done[s], c->stream));
+    if (prev_n > 0) {  // the batch before comes down while this one runs
+      HIP_TRY(hipEventSynchronize(pp.copied[s ^ 1]));
+      memcpy(out_cnt + prev_q0 * nr, pp.pin[s ^ 1], (size_t)prev_n * nr * 2);
+    }
+    HIP_TRY(hipStreamWaitEvent(pp.copy, pp.done[s], 0));
+    HIP_TRY(hipMemcpyAsync(pp.pin[s], d_cnt[s], (size_t)n * nr * 2, hipMemcpyDeviceToHost, pp.copy));
+    HIP_TRY(hipEventRecord(pp.copied[s], pp.copy));
+    prev_q0 = q0;
+    prev_n = n;
+  }
+  HIP_TRY(hipEventSynchronize(pp.copied[(b - 1) & 1]));
+  memcpy(out_cnt + prev_q0 * nr, pp.pin[(b - 1) & 1], (size_t)prev_n * nr * 2);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->pin_used = 0;  // the stream is idle: every staged upload has completed
+  return SBAG_OK;
+}
+
+static int check_prox_pair(sbag_ctx* c, const sbag_forest* f, const ProxRows& q, const ProxRows& r) {
+  TRY(check_prox_rows(c, f, q));
+  TRY(check_prox_rows(c, f, r));
+  if ((q.ds ? q.ds->F : q.F) != (r.ds ? r.ds->F : r.F))
+    return fail(SBAG_EINVAL, "the query and the reference rows differ in their feature count");
+  return SBAG_OK;
+}
+
+static int check_prox_groups(const ProxRows& r, const int32_t* ref_group, int32_t G) {
+  if (G < 1 || G > kProxMaxGroups)
+    return fail(SBAG_EINVAL, "num_groups must be in [1, " + std::to_string(kProxMaxGroups) + "]");
+  const int64_t nr = r.ds ? r.ds->N : r.N;
+  for (int64_t j = 0; j < nr; j++)
+    if (ref_group[j] < 0 || ref_group[j] >= G)
+      return fail(SBAG_EINVAL, "group id of reference row " + std::to_string(j) + " is outside [0, num_groups)");
+  return SBAG_OK;
+}
+
+static ProxRows prox_host_rows(const double* X, int64_t N, int32_t F) {
+  ProxRows r;
+  r.X = X;
+  r.N = N;
+  r.F = F;
+  return r;
+}
+static ProxRows prox_dataset_rows(const sbag_dataset* ds) {
+  ProxRows r;
+  r.ds = ds;
+  return r;
+}
+
+extern "C" {
+
+int sbag_proximity_tile(int32_t* block_rows, int32_t* block_cols) {
+  if (!block_rows || !block_cols) return fail(SBAG_EINVAL, "bad arguments");
+  *block_rows = kProxBM;
+  *block_cols = kProxBN;
+  return SBAG_OK;
+}
+
+int sbag_predict_leaves(sbag_ctx* c, const sbag_forest* f, const double* X, int64_t N, int32_t F, int32_t* out) {
+  if (!c || !f || !X || !out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  const ProxRows rows = prox_host_rows(X, N, F);
+  TRY(check_prox_rows(c, f, rows));
+  return leaves_run(c, f, rows, out);
+}
+
+int sbag_predict_leaves_dataset(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds, int32_t* out) {
+  if (!c || !f || !ds || !out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  const ProxRows rows = prox_dataset_rows(ds);
+  TRY(check_prox_rows(c, f, rows));
+  return leaves_run(c, f, rows, out);
+}
+
+int sbag_proximity(sbag_ctx* c, const sbag_forest* f, const double* Xq, int64_t nq, int32_t Fq, const double* Xr,
+                   int64_t nr, int32_t Fr, uint16_t* out) {
+  if (!c || !f || !Xq || !Xr || !out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  const ProxRows q = prox_host_rows(Xq, nq, Fq), r = prox_host_rows(Xr, nr, Fr);
+  TRY(check_prox_pair(c, f, q, r));
+  return prox_run(c, f, q, r, nullptr, 0, out, nullptr);
+}
+
+int sbag_proximity_dataset(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* dq, const sbag_dataset* dr,
+                           uint16_t* out) {
+  if (!c || !f || !dq || !dr || !out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  const ProxRows q = prox_dataset_rows(dq), r = prox_dataset_rows(dr);
+  TRY(check_prox_pair(c, f, q, r));
+  return prox_run(c, f, q, r, nullptr, 0, out, nullptr);
+}
+
+int sbag_proximity_moments(sbag_ctx* c, const sbag_forest* f, const double* Xq, int64_t nq, int32_t Fq,
+                           const double* Xr, int64_t nr, int32_t Fr, const int32_t* ref_group, int32_t num_groups,
+                           uint64_t* out) {
+  if (!c || !f || !Xq || !Xr || !ref_group || !out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  const ProxRows q = prox_host_rows(Xq, nq, Fq), r = prox_host_rows(Xr, nr, Fr);
+  TRY(check_prox_pair(c, f, q, r));
+  TRY(check_prox_groups(r, ref_group, num_groups));
+  return prox_run(c, f, q, r, ref_group, num_groups, nullptr, out);
+}
+
+int sbag_proximity_moments_dataset(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* dq,
+                                   const sbag_dataset* dr, const int32_t* ref_group, int32_t num_groups,
+                                   uint64_t* out) {
+  if (!c || !f || !dq || !dr || !ref_group || !out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  const ProxRows q = prox_dataset_rows(dq), r = prox_dataset_rows(dr);
+  TRY(check_prox_pair(c, f, q, r));
+  TRY(check_prox_groups(r, ref_group, num_groups));
+  return prox_run(c, f, q, r, ref_group, num_groups, nullptr, out);
 }
 
 }  // extern "C"

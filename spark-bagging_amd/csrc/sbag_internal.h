@@ -536,6 +536,41 @@ void launch_contrib_tiled(hipStream_t st, const ContribArgs& a);
 // launch_predict)
 void launch_contrib_walk(hipStream_t st, const double* X, const void* codes, int code_bytes,
                          const double* dict, const int64_t* dict_off, int32_t S, const ContribArgs& a);
+// ---- forest proximities (sbag_prox.hip): a row's leaf signature [tpad bytes] = its leaf code
+// in every tree (u8 / u16, sbag_prox_plan.h) and zero padding, and the pair counts of two
+// signature matrices by sbag.h's rule (sbag_proximity).
+struct LeafArgs {
+  unsigned char* sig;           // [rows][tpad]
+  int32_t tpad, code_bytes;     // bytes of a signature / of a leaf code
+  int32_t R, pad;               // k_leaf_tiled: rows of a tile
+};
+// k_leaf_tiled: k_quant_tiled's geometry at q.R rows a tile over a plan whose leaf nodes hold
+// 0x80000000 | leaf code; LDS = the R rows, a.chunk_bytes and prox_sig_lds(q.tpad, q.R)
+void launch_leaf_tiled(hipStream_t st, const PredictArgs& a, const LeafArgs& q);
+// k_leaf_walk: one thread per row of a batch of n over DevNodes in global memory (X fp64 rows,
+// or codes + dictionaries as launch_predict); a leaf's DevNode.pad is its code
+void launch_leaf_walk(hipStream_t st, const double* X, const void* codes, int code_bytes, const double* dict,
+                      const int64_t* dict_off, int64_t n, int32_t F, int32_t S, const DevNode* nodes,
+                      const int64_t* tree_off, int L, const LeafArgs& q);
+// k_leaf_ids: out int32 [n][L] = node_of[leaf_off[t] + code t of the row]
+void launch_leaf_ids(hipStream_t st, const LeafArgs& q, int64_t n, int L, const int32_t* node_of,
+                     const int64_t* leaf_off, int32_t* out);
+// k_sig_gather: dst row p = src row perm[p] of n signatures
+void launch_sig_gather(hipStream_t st, const unsigned char* src, const int64_t* perm, int64_t n, int tpad,
+                       unsigned char* dst);
+struct ProxColBlock;
+struct ProxArgs {
+  const unsigned char* sigq;    // [nq][tpad]
+  const unsigned char* sigr;    // [nr][tpad] (moments: in group order)
+  int64_t nq, nr;
+  int32_t tpad, code_bytes, L, G;
+  uint16_t* counts;             // counts mode: [nq][nr]
+  unsigned long long* moments;  // moments mode (not null): [nq][G][2], added to
+  const ProxColBlock* blocks;   // moments mode: the column blocks, [nblocks]
+  int32_t nblocks, run;         // ... and how many of them in a row one block takes
+};
+// k_prox_tiled: nq <= 65 535 * kProxBM rows a launch
+void launch_prox_tiled(hipStream_t st, const ProxArgs& p);
 // ---- out-of-bag predictions under permuted features (sbag_oobperm.hip): slot k of a
 // feature batch is sbag_predict_oob with feature feat[k] of row r taken from row src[k][r].
 // Between learner batches a slot's state lives in global memory as the baseline's does:

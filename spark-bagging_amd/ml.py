@@ -582,6 +582,45 @@ def permutation_source_rows(seed, repeat, feature, num_rows):
     return np.random.default_rng([seed, repeat, feature]).permutation(num_rows).astype(np.int32)
 
 
+class _ProxRows:
+    """The row sets of a leaf / proximity call as the library takes them: (ctx, rows), every
+    row set a host fp64 matrix, or every one a DeviceDataset.  Inputs as transform's (host rows,
+    a Frame, sparse rows, a DeviceDataset); None stands for the first row set.  Sparse rows, and
+    host rows beside a DeviceDataset, are binned into datasets that are freed on exit."""
+
+    def __init__(self, device, *inputs):
+        self.device, self.inputs, self.own = device, inputs, []
+
+    def __enter__(self):
+        rows = []
+        for raw in self.inputs:
+            x = raw.features if isinstance(raw, Frame) else raw
+            if rows and (raw is None or raw is self.inputs[0]):
+                rows.append(rows[0])
+            elif isinstance(x, nat.DeviceDataset) or is_sparse(x):
+                rows.append(x)
+            else:
+                x = np.asarray(x, np.float64)
+                rows.append(x[None, :] if x.ndim == 1 else x)
+        resident = [x for x in rows if isinstance(x, nat.DeviceDataset)]
+        ctx = resident[0].ctx if resident else nat.default_context(self.device)
+        if resident or any(is_sparse(x) for x in rows):
+            made = {}
+            for i, x in enumerate(rows):
+                if not isinstance(x, nat.DeviceDataset):
+                    if id(x) not in made:
+                        make = nat.DeviceDataset.from_csr if is_sparse(x) else nat.DeviceDataset.from_numpy
+                        made[id(x)] = make(x, np.zeros(x.shape[0]), ctx)
+                        self.own.append(made[id(x)])
+                    rows[i] = made[id(x)]
+        return ctx, rows
+
+    def __exit__(self, *exc):
+        for ds in self.own:
+            ds.free()
+        return False
+
+
 class _BaggingModel(_BaggingParams):
     _agg = None
 
@@ -658,6 +697,61 @@ class _BaggingModel(_BaggingParams):
         nat.predict_dataset_device(ds.ctx, forest, ds, nat.OUT_VOTES, 8, buf.data_ptr())
         torch.cuda.synchronize(dev)
         return pred, buf.cpu().numpy()
+
+    def predictLeaves(self, dataset, device=0):
+        """int32 [N, trees]: the node id of the leaf every row reaches in every tree (sklearn's
+        apply), walked on the device.  `dataset` as in transform; a DeviceDataset stays resident."""
+        forest = self.native_forest()
+        with _ProxRows(device, dataset) as (ctx, (rows,)):
+            if isinstance(rows, nat.DeviceDataset):
+                return nat.predict_leaves_dataset(ctx, forest, rows)
+            return nat.predict_leaves(ctx, forest, rows)
+
+    def proximity(self, queries, references=None, counts=False, device=0):
+        """fp64 [nq, nr]: the share of the trees that send query row i and reference row j to the
+        same leaf (randomForest's proximity = TRUE), counted on the device by one tiled all-pairs
+        kernel.  references None: the queries themselves.  counts: the raw uint16 pair counts."""
+        forest = self.native_forest()
+        with _ProxRows(device, queries, references) as (ctx, (q, r)):
+            if isinstance(q, nat.DeviceDataset):
+                cnt = nat.proximity_dataset(ctx, forest, q, r)
+            else:
+                cnt = nat.proximity(ctx, forest, q, r)
+        return cnt if counts else cnt / float(len(forest))
+
+    def proximityMoments(self, queries, references, groups, numGroups, device=0):
+        """uint64 [nq, numGroups, 2]: for every query row and every group of reference rows
+        (groups: int [nr] in [0, numGroups), numGroups <= 16) the sum of the pair counts and the
+        sum of their squares.  The pair matrix never leaves the device, so millions of query
+        rows against a few thousand references are usable."""
+        forest = self.native_forest()
+        with _ProxRows(device, queries, references) as (ctx, (q, r)):
+            if isinstance(q, nat.DeviceDataset):
+                return nat.proximity_moments_dataset(ctx, forest, q, r, groups, numGroups)
+            return nat.proximity_moments(ctx, forest, q, r, groups, numGroups)
+
+    def outlierMeasure(self, dataset, labels=None, device=0):
+        """randomForest's outlier(): raw_i = n / sum over the rows j of row i's class of
+        prox(i, j)^2 (j = i included), then within each class minus the median and over the
+        median absolute deviation (NumPy fp64).  A regression model has one class; a
+        classification model needs `labels`."""
+        n = dataset.shape[0] if not isinstance(dataset, Frame) else dataset.features.shape[0]
+        if labels is None:
+            if self._agg == nat.AGG_MODE:
+                raise nat.IllegalArgumentException(nat.SBAG_EINVAL, "outlierMeasure of a classifier needs labels")
+            labels = np.zeros(n)
+        classes, group = np.unique(np.asarray(labels).reshape(-1), return_inverse=True)
+        if len(group) != n:
+            raise nat.IllegalArgumentException(nat.SBAG_EINVAL, f"{len(group)} labels for {n} rows")
+        mom = self.proximityMoments(dataset, dataset, group, len(classes), device)
+        trees = float(self.numBaseModels)
+        out = np.zeros(n, np.float64)
+        for g in range(len(classes)):
+            own = group == g
+            raw = n / (mom[own, g, 1].astype(np.float64) / (trees * trees))
+            dev = raw - np.median(raw)
+            out[own] = dev / np.median(np.abs(dev))
+        return out
 
     def oobPredictions(self, dataset, partition_offsets=None):
         """Out-of-bag predictions on the training data: (pred, n_oob).  Row r is
