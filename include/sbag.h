@@ -674,7 +674,32 @@ int sbag_predict_contributions_dataset(sbag_ctx* ctx, const sbag_forest* f, cons
  * 65 535 thresholds and every call under SBAG_PROX_FORCE_FALLBACK=1 (read on every call) walk
  * global memory, one thread per row: the same signatures.  Stage B is one tiled all-pairs
  * kernel over the two signature matrices (sbag_proximity_tile: the pairs of one block), a packed
- * compare in the place of a multiply-add.                                                    */
+ * compare in the place of a multiply-add.
+ * sbag_proximity_topk(_dataset): the k nearest reference rows of every query row; the pair
+ *   matrix never leaves the kernel, nq x k entries come down.
+ *   Key.        Reference rows are ordered by the key (cnt(i, j), -j): the larger count first,
+ *               among equal counts the smaller j.  Keys are distinct for distinct j, so the
+ *               result is one well-defined array however the work is split.
+ *   Result.     idx_out is host int32 [nq x k], cnt_out host uint16 [nq x k], row-major: row i
+ *               holds the k largest keys of query row i in descending order, idx_out = j and
+ *               cnt_out = cnt(i, j).
+ *   Self.       self_offset >= 0 leaves reference row j == i + self_offset out of query row i's
+ *               candidates (queries that are rows [self_offset, self_offset + nq) of the
+ *               references); an offset past nr leaves nothing out.  self_offset == -1: none.
+ *   Short.      With fewer than k candidates the tail of a row is idx = -1, cnt = 0.
+ *   nq == 0 is SBAG_OK; nr == 0 gives all tails.  SBAG_EINVAL (nothing written, the context
+ *   stays usable): k outside [1, 64], self_offset < -1 and sbag_proximity's argument errors.
+ *   SBAG_EUNSUPPORTED: what sbag_proximity refuses.  The query rows go in batches, a batch's
+ *   result is 6 k bytes a row; a block of the pair kernel keeps the lists of its 128 query rows
+ *   in LDS over a run of column blocks, and a second kernel merges the runs' lists
+ *   (SBAG_PROX_TOPK_RUN=n, read on every call: n column blocks a run).                       */
+int sbag_proximity_topk(sbag_ctx* ctx, const sbag_forest* f, const double* Xq, int64_t nq,
+                        int32_t num_features_q, const double* Xr, int64_t nr, int32_t num_features_r,
+                        int32_t k, int64_t self_offset, int32_t* idx_out /* host [nq x k] */,
+                        uint16_t* cnt_out /* host [nq x k] */);
+int sbag_proximity_topk_dataset(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* queries,
+                                const sbag_dataset* references, int32_t k, int64_t self_offset,
+                                int32_t* idx_out, uint16_t* cnt_out);
 int sbag_proximity_tile(int32_t* block_rows, int32_t* block_cols);
 int sbag_predict_leaves(sbag_ctx* ctx, const sbag_forest* f, const double* X, int64_t num_rows,
                         int32_t num_features, int32_t* out /* host [num_rows x trees] */);

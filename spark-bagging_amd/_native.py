@@ -43,6 +43,7 @@ EXPORTED = [
     "sbag_predict_contributions", "sbag_predict_contributions_dataset",
     "sbag_proximity_tile", "sbag_predict_leaves", "sbag_predict_leaves_dataset",
     "sbag_proximity", "sbag_proximity_dataset", "sbag_proximity_moments", "sbag_proximity_moments_dataset",
+    "sbag_proximity_topk", "sbag_proximity_topk_dataset",
 ]
 
 
@@ -197,6 +198,8 @@ def lib():
             "sbag_proximity_dataset": [P, P, P, P, P],
             "sbag_proximity_moments": [P, P, P, i64, i32, P, i64, i32, P, i32, P],
             "sbag_proximity_moments_dataset": [P, P, P, P, P, i32, P],
+            "sbag_proximity_topk": [P, P, P, i64, i32, P, i64, i32, i32, i64, P, P],
+            "sbag_proximity_topk_dataset": [P, P, P, P, i32, i64, P, P],
             "sbag_forest_timing": [P, ctypes.POINTER(Timing)],
             "sbag_predict": [P, P, P, i64, i32, i32, P, P],
             "sbag_predict_dataset": [P, P, P, i32, P],
@@ -946,6 +949,29 @@ def proximity_moments_dataset(ctx, forest, queries, references, groups, num_grou
     check(lib().sbag_proximity_moments_dataset(ctx.handle, forest.handle, queries.handle, references.handle,
                                                ptr(g), int(num_groups), ptr(out)))
     return out
+
+
+def proximity_topk(ctx, forest, Xq, Xr, k, self_offset=-1):
+    """The k nearest host reference rows of every host query row (sbag_proximity_topk):
+    (int32 [nq, k] row indices, uint16 [nq, k] pair counts), the larger count first and among
+    equal counts the smaller index; reference row i + self_offset is left out of query row i
+    unless self_offset is -1; short lists end in (-1, 0)."""
+    Xq = np.ascontiguousarray(Xq, np.float64)
+    Xr = np.ascontiguousarray(Xr, np.float64)
+    idx = np.zeros((Xq.shape[0], max(int(k), 0)), np.int32)
+    cnt = np.zeros(idx.shape, np.uint16)
+    check(lib().sbag_proximity_topk(ctx.handle, forest.handle, ptr(Xq), Xq.shape[0], Xq.shape[1], ptr(Xr),
+                                    Xr.shape[0], Xr.shape[1], int(k), int(self_offset), ptr(idx), ptr(cnt)))
+    return idx, cnt
+
+
+def proximity_topk_dataset(ctx, forest, queries, references, k, self_offset=-1):
+    """proximity_topk over two device datasets (sbag_proximity_topk_dataset)."""
+    idx = np.zeros((queries.shape[0], max(int(k), 0)), np.int32)
+    cnt = np.zeros(idx.shape, np.uint16)
+    check(lib().sbag_proximity_topk_dataset(ctx.handle, forest.handle, queries.handle, references.handle, int(k),
+                                            int(self_offset), ptr(idx), ptr(cnt)))
+    return idx, cnt
 
 
 def predict_stacked(ctx, base, stack, X_or_dataset):

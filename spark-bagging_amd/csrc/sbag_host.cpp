@@ -6312,6 +6312,63 @@ static int prox_run(sbag_ctx* c, const sbag_forest* f, const ProxRows& q, const 
   return SBAG_OK;
 }
 
+// sbag_proximity_topk(_dataset): idx / cnt [nq][k].  The reference rows are split into runs of
+// column blocks (prox_topk_run, or SBAG_PROX_TOPK_RUN column blocks a run, read on every call);
+// the device holds one batch's signatures, partial lists and results.
+static int prox_topk_run_call(sbag_ctx* c, const sbag_forest* f, const ProxRows& q, const ProxRows& r, int32_t k,
+                              int64_t self_offset, int32_t* idx_out, uint16_t* cnt_out) {
+  ProxShape sh;
+  TRY(prox_shape(f, sh));
+  const int64_t nq = q.ds ? q.ds->N : q.N, nr = r.ds ? r.ds->N : r.N;
+  if (nr > INT32_MAX) return fail(SBAG_EUNSUPPORTED, "more than 2^31 - 1 reference rows");
+  if (nq == 0) return SBAG_OK;
+  if (nr == 0) {
+    std::fill(idx_out, idx_out + nq * k, (int32_t)-1);
+    std::fill(cnt_out, cnt_out + nq * k, (uint16_t)0);
+    return SBAG_OK;
+  }
+  HIP_TRY(hipSetDevice(c->device));
+  ProxArgs pa{};
+  pa.nr = nr;
+  pa.tpad = sh.tpad;
+  pa.code_bytes = sh.code_bytes;
+  pa.L = sh.L;
+  pa.nblocks = (int32_t)((nr + kProxBN - 1) / kProxBN);
+  unsigned char* d_sigr;
+  TRY(ws_typed(c, "px_sigr", (size_t)nr * sh.tpad, &d_sigr));
+  {
+    LeafRun R;
+    TRY(leaf_prepare(c, f, r, sh, R));
+    TRY(leaf_run(c, f, R, r, 0, nr, d_sigr));
+  }
+  pa.sigr = d_sigr;
+  LeafRun Q;
+  TRY(leaf_prepare(c, f, q, sh, Q));
+  const int64_t batch = std::min<int64_t>(prox_batch_topk(sh.tpad), (nq + kProxBM - 1) / kProxBM * kProxBM);
+  const char* forced = getenv("SBAG_PROX_TOPK_RUN");
+  unsigned char* d_sigq;
+  TopkArgs ta{};
+  ta.k = k;
+  TRY(ws_typed(c, "px_sigq", (size_t)batch * sh.tpad, &d_sigq));
+  TRY(ws_typed(c, "px_tkidx", (size_t)batch * k, &ta.idx));
+  TRY(ws_typed(c, "px_tkcnt", (size_t)batch * k, &ta.cnt));
+  pa.sigq = d_sigq;
+  for (int64_t q0 = 0; q0 < nq; q0 += batch) {
+    const int64_t n = std::min(batch, nq - q0);
+    TRY(leaf_run(c, f, Q, q, q0, n, d_sigq));
+    pa.nq = n;
+    pa.run = prox_topk_run((n + kProxBM - 1) / kProxBM, pa.nblocks, forced ? atoll(forced) : 0);
+    ta.nruns = (pa.nblocks + pa.run - 1) / pa.run;
+    ta.self_base = self_offset >= 0 ? q0 + self_offset : INT64_MIN / 2;
+    TRY(ws_typed(c, "px_tkpart", (size_t)n * ta.nruns * k, &ta.part));
+    launch_prox_topk(c->stream, pa, ta);
+    HIP_TRY(hipGetLastError());
+    TRY(d2h(c, idx_out + q0 * k, ta.idx, (size_t)n * k));
+    TRY(d2h(c, cnt_out + q0 * k, ta.cnt, (size_t)n * k));
+  }
+  return SBAG_OK;
+}
+
 static int check_prox_pair(sbag_ctx* c, const sbag_forest* f, const ProxRows& q, const ProxRows& r) {
   TRY(check_prox_rows(c, f, q));
   TRY(check_prox_rows(c, f, r));
@@ -6406,6 +6463,32 @@ int sbag_proximity_moments_dataset(sbag_ctx* c, const sbag_forest* f, const sbag
   TRY(check_prox_pair(c, f, q, r));
   TRY(check_prox_groups(r, ref_group, num_groups));
   return prox_run(c, f, q, r, ref_group, num_groups, nullptr, out);
+}
+
+static int check_prox_topk(int32_t k, int64_t self_offset) {
+  if (k < 1 || k > kTopkMaxK) return fail(SBAG_EINVAL, "k must be in [1, " + std::to_string(kTopkMaxK) + "]");
+  if (self_offset < -1) return fail(SBAG_EINVAL, "self_offset must be -1 (none) or a reference row index");
+  return SBAG_OK;
+}
+
+int sbag_proximity_topk(sbag_ctx* c, const sbag_forest* f, const double* Xq, int64_t nq, int32_t Fq, const double* Xr,
+                        int64_t nr, int32_t Fr, int32_t k, int64_t self_offset, int32_t* idx_out, uint16_t* cnt_out) {
+  if (!c || !f || !Xq || !Xr || !idx_out || !cnt_out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  const ProxRows q = prox_host_rows(Xq, nq, Fq), r = prox_host_rows(Xr, nr, Fr);
+  TRY(check_prox_pair(c, f, q, r));
+  TRY(check_prox_topk(k, self_offset));
+  return prox_topk_run_call(c, f, q, r, k, self_offset, idx_out, cnt_out);
+}
+
+int sbag_proximity_topk_dataset(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* dq, const sbag_dataset* dr,
+                                int32_t k, int64_t self_offset, int32_t* idx_out, uint16_t* cnt_out) {
+  if (!c || !f || !dq || !dr || !idx_out || !cnt_out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  const ProxRows q = prox_dataset_rows(dq), r = prox_dataset_rows(dr);
+  TRY(check_prox_pair(c, f, q, r));
+  TRY(check_prox_topk(k, self_offset));
+  return prox_topk_run_call(c, f, q, r, k, self_offset, idx_out, cnt_out);
 }
 
 }  // extern "C"

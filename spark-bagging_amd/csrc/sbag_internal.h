@@ -571,6 +571,18 @@ struct ProxArgs {
 };
 // k_prox_tiled: nq <= 65 535 * kProxBM rows a launch
 void launch_prox_tiled(hipStream_t st, const ProxArgs& p);
+// top-k mode: k_prox_topk over p's signatures (p.run column blocks a block, nruns runs), every
+// block's list into part [p.nq][nruns][k] (keys, sbag_prox_plan.h); then k_topk_merge, a wave a
+// row: the runs' lists into idx / cnt [p.nq][k].  Query row i leaves out column self_base + i
+// (a negative self_base below -p.nq: none).
+struct TopkArgs {
+  unsigned long long* part;
+  int32_t* idx;
+  uint16_t* cnt;
+  int64_t self_base;
+  int32_t k, nruns;
+};
+void launch_prox_topk(hipStream_t st, const ProxArgs& p, const TopkArgs& t);
 // ---- out-of-bag predictions under permuted features (sbag_oobperm.hip): slot k of a
 // feature batch is sbag_predict_oob with feature feat[k] of row r taken from row src[k][r].
 // Between learner batches a slot's state lives in global memory as the baseline's does:

@@ -37,6 +37,9 @@
 //     shuffles, lane tx == 0 adds into the row's u64 pair in LDS, and at every change of group
 //     the block adds the 128 pairs into out[row][group][2] with u64 atomics: integer sums, so
 //     the order is irrelevant.  With one K chunk (tpad <= 128) the query tile is staged once.
+//   k_prox_topk<ST>, k_topk_merge
+//     Top-k mode: the same tile and compare; the k best reference rows of every query row are
+//     kept in LDS over a run of column blocks and the runs' lists merged a wave a row (below).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -387,6 +390,255 @@ void launch_prox_tiled(hipStream_t st, const ProxArgs& p) {
     else
       hipLaunchKernelGGL((k_prox_tiled<uint16_t, false>), grid, dim3(kProxThreads), 0, st, p);
   }
+}
+
+// ---- top-k mode: the k best reference rows of every query row, selected while the block sweeps
+// its run of column blocks.  Row ty + 16 a of a tile is held by the 16 lanes of one ty, which lie
+// in one wave (ty >> 2): a row's list, staging area, fill count and bound are touched by that
+// wave alone, so the selection needs no barrier of the block, only the order in which one wave
+// issues its LDS operations.
+//   bound    dthr[row]: a pair passes iff diff < dthr.  L + 1 while the list has an empty place,
+//            then L - (the smallest count of the list): a pair that ties the list's last count
+//            comes from a later column, so it loses (sbag_prox_plan.h: the key).  0 for a row
+//            past the queries.  The bound only rises between merges, so a stale one lets too
+//            many through, never too few.
+//   filter   a lane takes the minimum of its 8 differences of a row (v_min3) and compares it
+//            with the bound: 8 broadcast LDS reads and fewer than 100 VALU operations a tile
+//            beside the 11 264 of the compare loop.  Only when some lane of the wave passes does the wave
+//            enter topk_collect.
+//   collect  every passing pair that is a real column (not the tail of the last block, not the
+//            row's own column) takes a place of the row's staging area through an LDS atomic on
+//            its fill count.  A pair that finds the area full stays pending; the wave merges its
+//            full rows, which raises their bounds, and the pending pairs try again: nothing is
+//            dropped, and every round places at least one key of every row that still has any.
+//   merge    by rank, no network: the list is sorted, the keys are distinct, so a key's place in
+//            the union is its own index plus the number of larger keys on the other side
+//            (counted with broadcast reads over the staging area, by bisection over the list).
+//            Every lane holds one list entry and one staged key, and the k largest go back
+//            sorted.  A row merges when its area is full and at the end of the run, not after
+//            every tile: the bound is then a little stale, and a row merges once per 16
+//            survivors instead of once per tile.
+__device__ __forceinline__ void wave_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// A: k keys, descending, the empty places (0) last.  B: nb <= 64 keys in any order, 0 = none.
+// Both in LDS and the calling wave's own.  The k largest of their union go into A, descending.
+__device__ __forceinline__ void topk_rank_merge(unsigned long long* A, int k, const unsigned long long* B, int nb,
+                                                int lane) {
+  const bool ina = lane < k, inb = lane < nb;
+  const unsigned long long a = ina ? A[lane] : 0ull, b = inb ? B[lane] : 0ull;
+  int ra = lane, rb = 0;  // an empty place of A goes behind every key of B and stays behind its own
+  for (int x = 0; x < nb; x++) {
+    const unsigned long long v = B[x];
+    ra += v > a ? 1 : 0;
+    rb += v > b ? 1 : 0;
+  }
+  int lo = 0, hi = inb && b != 0ull ? k : 0;  // the entries of A above b
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (A[mid] > b)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  rb += lo;
+  wave_lds_order();  // every lane has read A and B
+  if (ina && ra < k) A[ra] = a;
+  if (inb && b != 0ull && rb < k) A[rb] = b;
+  wave_lds_order();
+}
+
+struct TopkLds {
+  unsigned long long* list;   // [kProxBM][k]
+  unsigned long long* stage;  // [kProxBM][kTopkStage]
+  uint32_t* nstage;           // [kProxBM] keys asked for a place since the row's last merge
+  uint32_t* dthr;             // [kProxBM]
+};
+
+// the staged keys of one row into its list; the whole wave
+__device__ __forceinline__ void topk_flush(const TopkLds& S, int row, int k, uint32_t L, int lane) {
+  const uint32_t asked = S.nstage[row];
+  const int nb = asked < (uint32_t)kTopkStage ? (int)asked : kTopkStage;
+  topk_rank_merge(S.list + row * k, k, S.stage + row * kTopkStage, nb, lane);
+  if (lane == 0) {
+    const unsigned long long last = S.list[row * k + k - 1];
+    S.nstage[row] = 0u;
+    S.dthr[row] = last ? L - (uint32_t)(last >> 32) : L + 1u;
+  }
+  wave_lds_order();
+}
+
+// the rows of wave w: ty = 4 w + (lr & 3), a = lr >> 2
+__device__ __forceinline__ int topk_wave_row(int w, int lr) { return 4 * w + (lr & 3) + 16 * (lr >> 2); }
+
+// the wave's rows whose staging area holds at least `least` keys go into their lists
+__device__ __forceinline__ void topk_flush_rows(const TopkLds& S, int w, uint32_t least, int k, uint32_t L, int lane) {
+  unsigned long long due = __ballot(lane < 32 && S.nstage[topk_wave_row(w, lane & 31)] >= least);
+  while (due) {
+    const int lr = __ffsll((long long)due) - 1;
+    due &= due - 1;
+    topk_flush(S, topk_wave_row(w, lr), k, L, lane);
+  }
+}
+
+// the passing pairs of one tile into the staging areas of the wave's rows; the whole wave
+__device__ __forceinline__ void topk_collect(const TopkLds& S, const uint32_t (&diff)[kProxTM][kProxTN], int tx, int ty,
+                                             int64_t col0, int ncols, int64_t self0, int k, uint32_t L, int lane) {
+  unsigned long long pend = 0ull;  // bit 8 a + b: pair (a, b) still wants a place
+#pragma unroll
+  for (int a = 0; a < kProxTM; a++)
+#pragma unroll
+    for (int b = 0; b < kProxTN; b++) {
+      const int row = ty + 16 * a, col = tx + 16 * b;
+      if (diff[a][b] < S.dthr[row] && col < ncols && col0 + col != self0 + row) pend |= 1ull << (8 * a + b);
+    }
+  while (__any(pend != 0ull)) {
+#pragma unroll
+    for (int a = 0; a < kProxTM; a++)
+#pragma unroll
+      for (int b = 0; b < kProxTN; b++) {
+        const unsigned long long bit = 1ull << (8 * a + b);
+        if (pend & bit) {
+          const int row = ty + 16 * a;
+          if (diff[a][b] >= S.dthr[row]) {  // a merge has raised the bound since
+            pend &= ~bit;
+          } else {
+            const uint32_t slot = atomicAdd(&S.nstage[row], 1u);
+            if (slot < (uint32_t)kTopkStage) {
+              const uint32_t j = (uint32_t)(col0 + tx + 16 * b);
+              S.stage[row * kTopkStage + slot] = ((unsigned long long)(L - diff[a][b]) << 32) | (uint32_t)~j;
+              pend &= ~bit;
+            }
+          }
+        }
+      }
+    wave_lds_order();
+    topk_flush_rows(S, ty >> 2, (uint32_t)kTopkStage, k, L, lane);
+  }
+}
+
+// grid.x: the runs of column blocks; grid.y: the row blocks.  Dynamic LDS: prox_topk_lds(k).
+// The LDS admits two blocks a CU at most (sbag_prox_plan.h), two waves a SIMD, so the kernel
+// may take 256 registers a lane and is asked not to take more.
+template <typename ST>
+__global__ __launch_bounds__(kProxThreads, 2) void k_prox_topk(ProxArgs P, TopkArgs T) {
+  __shared__ __align__(16) unsigned char lds[kProxTileLds];
+  extern __shared__ __align__(16) unsigned char topk_lds[];
+  unsigned char* qt = lds;
+  unsigned char* rt = lds + kProxBM * kProxPitch;
+  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, lane = tid & 63, w = tid >> 6;
+  const int k = T.k;
+  const uint32_t L = (uint32_t)P.L;
+  TopkLds S;
+  S.list = (unsigned long long*)topk_lds;
+  S.stage = S.list + kProxBM * k;
+  S.nstage = (uint32_t*)(S.stage + kProxBM * kTopkStage);
+  S.dthr = S.nstage + kProxBM;
+  const int64_t row0 = (int64_t)blockIdx.y * kProxBM;
+  const int64_t qrows = P.nq - row0 < kProxBM ? P.nq - row0 : kProxBM;
+  const int nk = (P.tpad + kProxKC - 1) / kProxKC;
+  const int cb0 = (int)blockIdx.x * P.run;
+  const int cb1 = cb0 + P.run < P.nblocks ? cb0 + P.run : P.nblocks;
+  for (int i = lane; i < 32 * k; i += 64) {  // the wave's own 32 rows
+    const int lr = i / k;
+    S.list[topk_wave_row(w, lr) * k + (i - lr * k)] = 0ull;
+  }
+  if (lane < 32) {
+    const int row = topk_wave_row(w, lane);
+    S.nstage[row] = 0u;
+    S.dthr[row] = row < qrows ? L + 1u : 0u;
+  }
+  wave_lds_order();
+  for (int cb = cb0; cb < cb1; cb++) {
+    const int64_t col0 = (int64_t)cb * kProxBN;
+    const int ncols = (int)(P.nr - col0 < kProxBN ? P.nr - col0 : kProxBN);
+    uint32_t diff[kProxTM][kProxTN];
+#pragma unroll
+    for (int a = 0; a < kProxTM; a++)
+#pragma unroll
+      for (int b = 0; b < kProxTN; b++) diff[a][b] = 0u;
+    for (int kc = 0; kc < nk; kc++) {
+      const int k0 = kc * kProxKC;
+      const int pieces = (P.tpad - k0 < kProxKC ? P.tpad - k0 : kProxKC) >> 4;
+      block_sync();  // the previous chunk's reads are done
+      if (nk > 1 || cb == cb0) prox_stage(qt, P.sigq, P.tpad, row0, qrows, k0, pieces, kProxBM, tid);
+      prox_stage(rt, P.sigr, P.tpad, col0, ncols, k0, pieces, kProxBN, tid);
+      block_sync();
+      for (int p = 0; p < pieces; p++) {
+        uint4 qv[kProxTM];
+#pragma unroll
+        for (int a = 0; a < kProxTM; a++) qv[a] = *(const uint4*)(qt + (ty + 16 * a) * kProxPitch + p * 16);
+#pragma unroll
+        for (int b = 0; b < kProxTN; b++) {
+          const uint4 rv = *(const uint4*)(rt + (tx + 16 * b) * kProxPitch + p * 16);
+#pragma unroll
+          for (int a = 0; a < kProxTM; a++) {
+            uint32_t d = diff[a][b];
+            d = add_nonzero_codes<ST>(qv[a].x ^ rv.x, d);
+            d = add_nonzero_codes<ST>(qv[a].y ^ rv.y, d);
+            d = add_nonzero_codes<ST>(qv[a].z ^ rv.z, d);
+            d = add_nonzero_codes<ST>(qv[a].w ^ rv.w, d);
+            diff[a][b] = d;
+          }
+        }
+      }
+    }
+    bool pass = false;
+#pragma unroll
+    for (int a = 0; a < kProxTM; a++) {
+      uint32_t m = diff[a][0];
+#pragma unroll
+      for (int b = 1; b < kProxTN; b++) m = m < diff[a][b] ? m : diff[a][b];
+      pass |= m < S.dthr[ty + 16 * a];
+    }
+    if (__any(pass)) topk_collect(S, diff, tx, ty, col0, ncols, T.self_base + row0, k, L, lane);
+  }
+  topk_flush_rows(S, w, 1u, k, L, lane);
+  unsigned long long* out = T.part + (row0 * T.nruns + blockIdx.x) * k;
+  for (int i = lane; i < 32 * k; i += 64) {
+    const int lr = i / k, e = i - lr * k, row = topk_wave_row(w, lr);
+    if (row < qrows) out[(int64_t)row * T.nruns * k + e] = S.list[row * k + e];
+  }
+}
+
+// a wave a row: the row's nruns lists (each descending) into one, and keys into (index, count)
+__global__ __launch_bounds__(256) void k_topk_merge(TopkArgs T, int64_t nq) {
+  __shared__ unsigned long long buf[4][2][kTopkMaxK];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * 4 + w;
+  if (row >= nq) return;  // the whole wave
+  const int k = T.k;
+  unsigned long long* A = buf[w][0];
+  unsigned long long* B = buf[w][1];
+  const unsigned long long* p = T.part + row * T.nruns * k;
+  if (lane < k) A[lane] = p[lane];
+  for (int r = 1; r < T.nruns; r++) {
+    if (lane < k) B[lane] = p[(int64_t)r * k + lane];
+    wave_lds_order();
+    topk_rank_merge(A, k, B, k, lane);
+  }
+  wave_lds_order();
+  if (lane < k) {
+    const unsigned long long key = A[lane];
+    T.idx[row * k + lane] = key ? (int32_t)~(uint32_t)key : -1;
+    T.cnt[row * k + lane] = (uint16_t)(key >> 32);
+  }
+}
+
+void launch_prox_topk(hipStream_t st, const ProxArgs& p, const TopkArgs& t) {
+  const dim3 grid((unsigned)t.nruns, (unsigned)((p.nq + kProxBM - 1) / kProxBM));
+  const size_t lds = prox_topk_lds(t.k);
+  if (p.code_bytes == 1) {
+    leaf_set_max_lds((const void*)k_prox_topk<uint8_t>, (int)prox_topk_lds(kTopkMaxK));
+    hipLaunchKernelGGL((k_prox_topk<uint8_t>), grid, dim3(kProxThreads), lds, st, p, t);
+  } else {
+    leaf_set_max_lds((const void*)k_prox_topk<uint16_t>, (int)prox_topk_lds(kTopkMaxK));
+    hipLaunchKernelGGL((k_prox_topk<uint16_t>), grid, dim3(kProxThreads), lds, st, p, t);
+  }
+  hipLaunchKernelGGL(k_topk_merge, dim3((unsigned)((p.nq + 3) / 4)), dim3(256), 0, st, t, p.nq);
 }
 
 }  // namespace sbag

@@ -65,6 +65,35 @@ inline int64_t prox_batch_moments(int tpad) {
   return std::max<int64_t>(kProxBM, std::min<int64_t>(((int64_t)64 << 20) / tpad, 65536) / kProxBM * kProxBM);
 }
 
+// ---- top-k mode (k_prox_topk).  A key is cnt << 32 | ~j: larger count first, among equal counts
+// the smaller j; j < 2^31, so a key of a pair is never 0 and 0 stands for "no entry".  Beside
+// the two signature tiles a block holds, per query row of its tile, a list of k keys (descending),
+// a staging area of kTopkStage keys, the area's fill count and the row's filter bound (u32
+// each): kProxTileLds + prox_topk_lds(k) bytes, the second part dynamic and sized from k.
+//   k <= 26: 36 864 + 44 032 = 80 896 B at most, two blocks a CU (the staging area alone
+//            is 16 KB, so no k reaches three)
+//   k <= 64: 36 864 + 82 944 = 119 808 B at most, one block a CU
+constexpr int kTopkMaxK = 64;
+constexpr int kTopkStage = 16;
+constexpr size_t prox_topk_lds(int k) { return (size_t)kProxBM * ((size_t)(k + kTopkStage) * 8 + 8); }
+static_assert(kProxTileLds + prox_topk_lds(26) <= (160 * 1024) / 2, "k <= 26: two blocks a CU");
+static_assert(kProxTileLds + prox_topk_lds(kTopkMaxK) <= kProxLdsCap, "the largest k fits the LDS");
+static_assert(kTopkMaxK <= 64 && kTopkStage <= 64, "a merge holds one list entry and one staged key a lane");
+static_assert(kProxMaxTrees < (1 << 16), "a key's count is stored as a u16");
+// the column blocks one block of k_prox_topk takes in a row: `forced` (SBAG_PROX_TOPK_RUN) if
+// positive, else enough runs to fill the device (as moments mode: 2048 blocks a launch)
+inline int32_t prox_topk_run(int64_t row_blocks, int64_t nblocks, int64_t forced) {
+  if (forced > 0) return (int32_t)std::min<int64_t>(forced, std::max<int64_t>(nblocks, 1));
+  const int64_t xs = std::max<int64_t>(1, std::min<int64_t>(nblocks, (2048 + row_blocks - 1) / row_blocks));
+  return (int32_t)((nblocks + xs - 1) / xs);
+}
+// query rows of a batch: 64 MB of signatures at most, 32 768 rows at most (256 block rows), so
+// that the partial lists [rows][runs][k] of a launch of at most 2048 + 256 blocks stay below
+// 128 x 2304 x 64 x 8 B = 151 MB
+inline int64_t prox_batch_topk(int tpad) {
+  return std::max<int64_t>(kProxBM, std::min<int64_t>(((int64_t)64 << 20) / tpad, 32768) / kProxBM * kProxBM);
+}
+
 struct ProxColBlock {  // columns [col0, col0 + ncols) of the ordered reference rows, ncols <= kProxBN
   int32_t col0, ncols, group, pad;
 };

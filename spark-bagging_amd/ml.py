@@ -730,6 +730,20 @@ class _BaggingModel(_BaggingParams):
                 return nat.proximity_moments_dataset(ctx, forest, q, r, groups, numGroups)
             return nat.proximity_moments(ctx, forest, q, r, groups, numGroups)
 
+    def nearestNeighbors(self, queries, references=None, k=10, excludeSelf=None, device=0):
+        """(int32 [nq, k] indices, fp64 [nq, k] proximities): the k reference rows nearest to
+        every query row by forest proximity, the nearest first and among equal proximities the
+        smaller index, selected inside the pair kernel (k <= 64; the pair matrix is never
+        formed).  references None: the queries themselves, and excludeSelf then defaults to
+        True: row i is left out of its own neighbours.  Short lists end in (-1, 0.0)."""
+        forest = self.native_forest()
+        if excludeSelf is None:
+            excludeSelf = references is None
+        with _ProxRows(device, queries, references) as (ctx, (q, r)):
+            topk = nat.proximity_topk_dataset if isinstance(q, nat.DeviceDataset) else nat.proximity_topk
+            idx, cnt = topk(ctx, forest, q, r, k, 0 if excludeSelf else -1)
+        return idx, cnt / float(len(forest))
+
     def outlierMeasure(self, dataset, labels=None, device=0):
         """randomForest's outlier(): raw_i = n / sum over the rows j of row i's class of
         prox(i, j)^2 (j = i included), then within each class minus the median and over the
