@@ -522,6 +522,62 @@ int sbag_predict_oob_quantiles(sbag_ctx* ctx, const sbag_forest* f, const sbag_d
                                const sbag_sampler_params* sampler, const int64_t* partition_offsets,
                                int32_t num_partitions, const double* probs, int32_t num_probs,
                                double* out, int32_t* n_oob_out /* host [num_rows] or NULL */);
+/* ---- the sampling variance of a bagged prediction: the infinitesimal jackknife of Efron (2014)
+ * and Wager, Hastie & Efron (2014) (ranger's se.method = "infjack", forestci), for regression
+ * forests.  With c[b][i] the bag count of training row i in learner b, t_b the trees'
+ * predictions of a row, m their mean, d_b = t_b - m and T trees,
+ *   V_IJ = (1 / T^2) sum_i ( sum_b c[b][i] d_b )^2 = (1 / T^2) d' G d,  G[a][b] = sum_i c[a][i] c[b][i]
+ * (sum_b d_b = 0: centring the counts changes nothing).  G does not depend on the row.
+ *
+ * The Gram matrix.  gram_out is host int64 [T x T], row-major, full and symmetric, exact:
+ * gram_out[a][b] = sum_r counts[a][r] * counts[b][r].  sbag_bag_gram draws the counts of the
+ * sampler's learners [learner_begin, learner_end) on the device (sbag_sample's bytes, its
+ * validation and error codes; no count leaves the device); sbag_counts_gram takes counts the
+ * caller kept (host u8 [T x num_rows], any byte value).  1 <= T <= 1024, else
+ * SBAG_EUNSUPPORTED; sbag_bag_gram also returns SBAG_EUNSUPPORTED when the counts (T x num_rows
+ * bytes) do not fit one learner batch of sbag_predict_oob (or SBAG_OOB_BATCH_LEARNERS is below
+ * T).  num_rows == 0 gives zeros.  Bytes below 128 are contracted by int8 matrix instructions;
+ * a count from 128 up, and every call under SBAG_GRAM_FORCE_FALLBACK=1 (read on every call),
+ * takes packed-byte dot products: the same integers.
+ *
+ * The variance.  out is host fp64 [num_rows x 3], row-major: out[r] = { m, v_ij, v_iju }.
+ * Every fp64 operation below is rounded on its own, with no FMA.
+ *   - t_b is tree b's prediction of the row.  Routing is exactly sbag_predict's.
+ *   - s = 0.0; s = s + t_b for b = 0..T-1, then m = s / (double)T.  These are byte for byte
+ *     sbag_predict's SBAG_AGG_MEAN output.
+ *   - d_b = t_b - m.
+ *   - Only the diagonal and the lower triangle of gram are read.  Write
+ *     Gd[a][b] = (double)gram[a][b].  An entry that is negative or >= 2^53 is SBAG_EINVAL.
+ *   - Start with q = 0.0; c = 0.0;.  For a = 0..T-1:
+ *       s = 0.0; and for b = 0..a-1: s = s + Gd[a][b] * d_b;
+ *       u = (s + s) + Gd[a][a] * d_a;
+ *       q = q + d_a * u;
+ *       c = c + d_a * d_a;
+ *   - v_ij = q / (double)(T * T).
+ *   - On the host, in exact int64: tr = sum_a gram[a][a], tot = tr + 2 sum_{b<a} gram[a][b],
+ *     w = (double)tr / (double)T - (double)tot / (double)(T * T).  A tot that overflows int64 is
+ *     SBAG_EINVAL.
+ *   - v_iju = v_ij - (w * c) / (double)(T * T).
+ *   - Neither variance is clamped.  A negative v_iju is a legitimate Monte-Carlo outcome.
+ * v_iju is the Monte-Carlo bias correction of Wager et al.: w = sum_i Var_b(c[b][i]) is the
+ * empirical form of their n, right for Poisson bags of any ratio and for Bernoulli bags too.
+ * SBAG_EINVAL (nothing written, the context stays usable): a null argument, a gini forest, a
+ * leaf that predicts NaN, the gram errors above, and the argument errors of sbag_predict /
+ * sbag_predict_dataset.  SBAG_EUNSUPPORTED: more than 1024 trees.  num_rows == 0 is SBAG_OK.
+ * u8 / u16 codes and a row tile (256, 128, 64 or 32 rows) whose rows, fp64 matrix [T x rows] and
+ * a forest chunk fit the LDS go through one fused pass that walks the trees and forms the
+ * variance; u32 codes, larger trees, a T whose matrix fits no tile, and every call under
+ * SBAG_IJ_FORCE_FALLBACK=1 (read on every call) write per-tree predictions to a workspace a row
+ * batch at a time and form the variance in a second kernel: the same bits.                 */
+int sbag_bag_gram(sbag_ctx* ctx, const sbag_sampler_params* sampler, const int64_t* partition_offsets,
+                  int32_t num_partitions, int64_t num_rows, int64_t* gram_out /* host [T x T] */);
+int sbag_counts_gram(sbag_ctx* ctx, const uint8_t* counts /* host [T x num_rows] */, int32_t T,
+                     int64_t num_rows, int64_t* gram_out /* host [T x T] */);
+int sbag_predict_variance(sbag_ctx* ctx, const sbag_forest* f, const double* X, int64_t num_rows,
+                          int32_t num_features, const int64_t* gram /* host [T x T] */,
+                          double* out /* host [num_rows x 3] */);
+int sbag_predict_variance_dataset(sbag_ctx* ctx, const sbag_forest* f, const sbag_dataset* ds,
+                                  const int64_t* gram, double* out);
 /* ---- partial dependence of the ensemble on one feature (randomForest's partialPlot, sklearn's
  * partial_dependence): how the prediction, averaged over the rows, moves when feature `feature`
  * (a global index) of every row is set to each of the grid's values in turn.

@@ -44,6 +44,7 @@ EXPORTED = [
     "sbag_proximity_tile", "sbag_predict_leaves", "sbag_predict_leaves_dataset",
     "sbag_proximity", "sbag_proximity_dataset", "sbag_proximity_moments", "sbag_proximity_moments_dataset",
     "sbag_proximity_topk", "sbag_proximity_topk_dataset",
+    "sbag_bag_gram", "sbag_counts_gram", "sbag_predict_variance", "sbag_predict_variance_dataset",
 ]
 
 
@@ -187,6 +188,10 @@ def lib():
             "sbag_predict_quantiles": [P, P, P, i64, i32, P, i32, P],
             "sbag_predict_quantiles_dataset": [P, P, P, P, i32, P],
             "sbag_predict_oob_quantiles": [P, P, P, ctypes.POINTER(SamplerParams), P, i32, P, i32, P, P],
+            "sbag_bag_gram": [P, ctypes.POINTER(SamplerParams), P, i32, i64, P],
+            "sbag_counts_gram": [P, P, i32, i64, P],
+            "sbag_predict_variance": [P, P, P, i64, i32, P, P],
+            "sbag_predict_variance_dataset": [P, P, P, P, P],
             "sbag_partial_dependence": [P, P, P, i64, i32, i32, P, i32, i32, i32, P, P, P],
             "sbag_partial_dependence_dataset": [P, P, P, i32, P, i32, i32, i32, P, P, P],
             "sbag_predict_contributions": [P, P, P, i64, i32, i32, P, P],
@@ -816,6 +821,51 @@ def predict_oob_quantiles(ctx, forest, dataset, probs, *, replacement, sample_ra
     check(lib().sbag_predict_oob_quantiles(ctx.handle, forest.handle, dataset.handle, ctypes.byref(sp), ptr(off),
                                            P, ptr(p), len(p), ptr(out), ptr(n_oob)))
     return out, n_oob
+
+
+def bag_gram(ctx, *, replacement, sample_ratio, seed, learner_begin, learner_end, num_rows,
+             partition_offsets=None):
+    """The Gram matrix of the sampler's bag counts (sbag_bag_gram): int64 [T, T],
+    G[a][b] = sum_r counts[a][r] * counts[b][r] for sample()'s counts, contracted on the device."""
+    sp = SamplerParams(int(replacement), 0, float(sample_ratio), int(seed), learner_begin, learner_end)
+    off = None
+    P = 1
+    if partition_offsets is not None:
+        off = np.ascontiguousarray(partition_offsets, np.int64)
+        P = len(off) - 1
+    T = max(learner_end - learner_begin, 0)
+    out = np.zeros((T, T), np.int64)
+    check(lib().sbag_bag_gram(ctx.handle, ctypes.byref(sp), ptr(off), P, int(num_rows), ptr(out)))
+    return out
+
+
+def counts_gram(ctx, counts):
+    """The Gram matrix of counts the caller kept (sbag_counts_gram): u8 [T, N] -> int64 [T, T]."""
+    counts = np.ascontiguousarray(counts, np.uint8)
+    T, n = counts.shape
+    out = np.zeros((T, T), np.int64)
+    check(lib().sbag_counts_gram(ctx.handle, ptr(counts) if counts.size else ptr(np.zeros(1, np.uint8)), T, n,
+                                 ptr(out)))
+    return out
+
+
+def predict_variance(ctx, forest, X, gram):
+    """The bagged mean and its infinitesimal-jackknife variance for host rows
+    (sbag_predict_variance): fp64 [N, 3] = (m, v_ij, v_iju), sbag.h's rule."""
+    X = np.ascontiguousarray(X, np.float64)
+    g = np.ascontiguousarray(gram, np.int64)
+    out = np.zeros((X.shape[0], 3), np.float64)
+    check(lib().sbag_predict_variance(ctx.handle, forest.handle, ptr(X), X.shape[0], X.shape[1], ptr(g),
+                                      ptr(out)))
+    return out
+
+
+def predict_variance_dataset(ctx, forest, dataset, gram):
+    """predict_variance over a device dataset (sbag_predict_variance_dataset)."""
+    g = np.ascontiguousarray(gram, np.int64)
+    out = np.zeros((dataset.shape[0], 3), np.float64)
+    check(lib().sbag_predict_variance_dataset(ctx.handle, forest.handle, dataset.handle, ptr(g), ptr(out)))
+    return out
 
 
 def _pd_call(forest, grid, kind, num_classes, weights, per_tree, call):

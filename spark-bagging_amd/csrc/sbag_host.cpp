@@ -33,6 +33,7 @@
 #include "sbag.h"
 #include "sbag_budget.h"
 #include "sbag_fastmath.h"
+#include "sbag_ij_plan.h"
 #include "sbag_internal.h"
 #include "sbag_mfma_plan.h"
 #include "sbag_pd_plan.h"
@@ -5965,6 +5966,276 @@ int sbag_predict_oob_quantiles(sbag_ctx* c, const sbag_forest* f, const sbag_dat
   }
   TRY(quant_dataset(c, f, ds, probs, num_probs, R, out));
   if (n_oob_out && N > 0) TRY(d2h(c, n_oob_out, R.q.n_oob, (size_t)N));
+  return SBAG_OK;
+}
+
+}  // extern "C"
+
+// ---- infinitesimal-jackknife variance (sbag_ij.hip).  The Gram matrix of counts u8 [T][N] on
+// the device (readable past its end: the workspace's slack): k_gram_mfma, and k_gram_dot when
+// that kernel saw a byte >= 128 or SBAG_GRAM_FORCE_FALLBACK is set (read on every call).  The
+// kernels fill the lower triangle; the host mirrors it.
+static int gram_run(sbag_ctx* c, const uint8_t* d_counts, int T, int64_t N, int64_t* gram_out) {
+  std::fill(gram_out, gram_out + (size_t)T * T, (int64_t)0);
+  if (N == 0) return SBAG_OK;
+  unsigned long long* d_gram;
+  int* d_flag;
+  TRY(ws_typed(c, "gram_acc", (size_t)T * T, &d_gram));
+  TRY(ws_typed(c, "gram_flag", 1, &d_flag));
+  const char* ffb = getenv("SBAG_GRAM_FORCE_FALLBACK");
+  bool dot = ffb && atoi(ffb) != 0;
+  for (;;) {
+    HIP_TRY(hipMemsetAsync(d_gram, 0, (size_t)T * T * 8, c->stream));
+    HIP_TRY(hipMemsetAsync(d_flag, 0, 4, c->stream));
+    launch_gram(c->stream, d_counts, T, N, d_gram, d_flag, dot);
+    HIP_TRY(hipGetLastError());
+    if (dot) break;
+    int flag = 0;
+    TRY(d2h(c, &flag, d_flag, 1));
+    if (!flag) break;
+    dot = true;  // a byte past int8: the general kernel
+  }
+  TRY(d2h(c, (unsigned long long*)gram_out, d_gram, (size_t)T * T));
+  for (int a = 0; a < T; a++)
+    for (int b = 0; b < a; b++) gram_out[(size_t)b * T + a] = gram_out[(size_t)a * T + b];
+  return SBAG_OK;
+}
+
+static int check_gram_learners(int T) {
+  if (T > kGramMaxLearners)
+    return fail(SBAG_EUNSUPPORTED, "a Gram matrix over " + std::to_string(T) + " learners (limit " +
+                                       std::to_string(kGramMaxLearners) + ")");
+  return SBAG_OK;
+}
+
+// what a variance call checks of its forest and Gram matrix; the fp64 copy of the diagonal and
+// lower triangle (the rest +0.0) and sbag.h's w
+static int check_variance(const sbag_forest* f, const int64_t* gram, std::vector<double>& Gd, double* w) {
+  if (f->impurity == SBAG_IMPURITY_GINI) return fail(SBAG_EINVAL, "the variance needs a regression forest");
+  const int T = (int)f->trees.size();
+  if (T > kIjMaxTrees)
+    return fail(SBAG_EUNSUPPORTED, "the variance over " + std::to_string(T) + " trees (limit " +
+                                       std::to_string(kIjMaxTrees) + ")");
+  for (const HTree& t : f->trees)
+    for (const sbag_node& n : t.nodes)
+      if (n.left < 0 && n.prediction != n.prediction) return fail(SBAG_EINVAL, "a leaf predicts NaN");
+  Gd.assign((size_t)T * T, 0.0);
+  int64_t tr = 0, off = 0;
+  bool over = false;
+  for (int a = 0; a < T; a++)
+    for (int b = 0; b <= a; b++) {
+      const int64_t g = gram[(size_t)a * T + b];
+      if (g < 0 || g >= ((int64_t)1 << 53))
+        return fail(SBAG_EINVAL, "gram[" + std::to_string(a) + "][" + std::to_string(b) + "] is outside [0, 2^53)");
+      Gd[(size_t)a * T + b] = (double)g;
+      over |= __builtin_add_overflow(a == b ? tr : off, g, a == b ? &tr : &off);
+    }
+  int64_t tot = 0;
+  over |= __builtin_add_overflow(off, off, &tot);
+  over |= __builtin_add_overflow(tot, tr, &tot);
+  if (over) return fail(SBAG_EINVAL, "the sum of the Gram matrix overflows int64");
+  const double tt = (double)((int64_t)T * T);
+  *w = (double)tr / (double)T - (double)tot / tt;
+  return SBAG_OK;
+}
+
+struct IjRun {
+  bool tiled = false;
+  PredictArgs pa{};                // tiled: the uploaded plan (codes / N set per launch)
+  const DevNode* nodes = nullptr;  // general path
+  const int64_t* off = nullptr;
+  double* tp = nullptr;            // general path: per-tree predictions [T][batch]
+  int64_t batch = 0;
+  IjArgs q{};
+};
+
+// the plan of a variance pass over codes of `code_bytes` at row stride S (tc_of as plan_tiled's),
+// uploaded with the fp64 Gram matrix; may_tile false: the general path, its workspace sized for N
+template <typename TC>
+static int ij_prepare(sbag_ctx* c, const sbag_forest* f, const std::vector<double>& Gd, double w, int code_bytes,
+                      int S, int F, bool may_tile, int64_t N, TC tc_of, IjRun& R) {
+  const int T = (int)f->trees.size();
+  const char* ffb = getenv("SBAG_IJ_FORCE_FALLBACK");
+  if (ffb && atoi(ffb) != 0) may_tile = false;
+  double* d_G;
+  TRY(ws_typed(c, "ij_gram", std::max<size_t>(Gd.size(), 1), &d_G));
+  TRY(h2d(c, d_G, Gd.data(), Gd.size()));
+  R.q.G = d_G;
+  R.q.w = w;
+  R.q.tt = (double)((int64_t)T * T);
+  R.pa.code_bytes = code_bytes;
+  R.pa.S = S;
+  R.pa.agg = kAggMean;  // predict_tiled_lds: the row tile and the chunk; the matrix is extra
+  const int Rt = may_tile ? ij_tile_rows(S * code_bytes + 4, T) : 0;
+  TiledPlan P;
+  R.tiled = Rt > 0 && plan_tiled(f, R.pa, F, tc_of, P, ij_matrix_lds(T, Rt), 0, Rt);
+  if (R.tiled) {
+    R.q.R = Rt;
+    return upload_plan(c, P, R.pa);
+  }
+  TRY(upload_forest(c, f, &R.nodes, &R.off));
+  R.batch = std::max<int64_t>(1, std::min<int64_t>(N, ((int64_t)256 << 20) / (8 * (int64_t)std::max(T, 1))));
+  TRY(ws_typed(c, "ij_tp", (size_t)R.batch * std::max(T, 1), &R.tp));
+  return SBAG_OK;
+}
+
+// the general path over N rows (X fp64 rows on the device, or a dataset's codes): the per-tree
+// predict path into R.tp, then k_ij_form; R.q.out set for row 0
+static int ij_general(sbag_ctx* c, const IjRun& R, const double* d_X, const sbag_dataset* ds, int64_t N, int F,
+                      int T) {
+  for (int64_t r0 = 0; r0 < N; r0 += R.batch) {
+    const int64_t n = std::min(R.batch, N - r0);
+    IjArgs q = R.q;
+    q.out = R.q.out + r0 * 3;
+    if (d_X)
+      launch_predict(c->stream, d_X + r0 * F, nullptr, 1, nullptr, nullptr, n, F, F, R.nodes, R.off, T,
+                     kAggVotes, 1, nullptr, nullptr, R.tp, 8, nullptr, 0);
+    else
+      launch_predict(c->stream, nullptr, (const unsigned char*)ds->d_codes + (size_t)r0 * ds->S * ds->code_bytes,
+                     ds->code_bytes, ds->d_dict, ds->d_dict_off, n, ds->F, ds->S, R.nodes, R.off, T, kAggVotes, 1,
+                     nullptr, nullptr, R.tp, 8, nullptr, 0);
+    HIP_TRY(hipGetLastError());
+    launch_ij_form(c->stream, R.tp, n, T, q);
+    HIP_TRY(hipGetLastError());
+  }
+  return SBAG_OK;
+}
+
+extern "C" {
+
+int sbag_bag_gram(sbag_ctx* c, const sbag_sampler_params* sp, const int64_t* partition_offsets, int32_t P,
+                  int64_t N, int64_t* gram_out) {
+  if (!c || !sp || !gram_out || N < 0) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(check_sampler(sp));
+  std::vector<int64_t> poff;
+  TRY(check_partitions(P, partition_offsets, N, poff));
+  const int T = sp->learner_end - sp->learner_begin;
+  TRY(check_gram_learners(T));
+  HIP_TRY(hipSetDevice(c->device));
+  uint8_t* d_counts = nullptr;
+  if (N > 0) {
+    // the contraction needs every learner's counts at once: one batch, as the out-of-bag quantiles
+    int batch = (int)std::max(1.0, std::min((double)T, std::floor(bins_budget(c) / (double)N)));
+    if (const char* e = getenv("SBAG_OOB_BATCH_LEARNERS")) batch = std::max(1, std::min(T, atoi(e)));
+    if (batch < T)
+      return fail(SBAG_EUNSUPPORTED, "the Gram matrix needs the bag counts of all " + std::to_string(T) +
+                                         " learners at once; " + std::to_string(batch) + " fit a batch");
+    TRY(ws_typed(c, "counts", (size_t)T * N, &d_counts));
+    TRY(run_sampler(c, sp, poff, N, d_counts));
+  }
+  return gram_run(c, d_counts, T, N, gram_out);
+}
+
+int sbag_counts_gram(sbag_ctx* c, const uint8_t* counts, int32_t T, int64_t N, int64_t* gram_out) {
+  if (!c || !counts || !gram_out || N < 0 || T < 1) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(check_gram_learners(T));
+  HIP_TRY(hipSetDevice(c->device));
+  uint8_t* d_counts = nullptr;
+  if (N > 0) {
+    TRY(ws_typed(c, "counts", (size_t)T * N, &d_counts));
+    TRY(h2d(c, d_counts, counts, (size_t)T * N));
+  }
+  return gram_run(c, d_counts, T, N, gram_out);
+}
+
+int sbag_predict_variance(sbag_ctx* c, const sbag_forest* f, const double* X, int64_t N, int32_t F,
+                          const int64_t* gram, double* out) {
+  if (!c || !f || !X || !gram || !out || N < 0 || F <= 0) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  std::vector<double> Gd;
+  double w = 0.0;
+  TRY(check_variance(f, gram, Gd, &w));
+  for (const HTree& t : f->trees)
+    for (int32_t g : t.sub)
+      if (g >= F) return fail(SBAG_EINVAL, "feature vector shorter than a subspace index");
+  if (N == 0) return SBAG_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  const int T = (int)f->trees.size();
+  // rows are binned on the device against the forest's own thresholds, as in sbag_predict
+  std::vector<std::vector<double>> Th(F);
+  for (const HTree& t : f->trees)
+    for (const sbag_node& n : t.nodes)
+      if (n.left >= 0) Th[t.sub[n.feature]].push_back(n.threshold);
+  std::vector<int64_t> toff(F + 1, 0);
+  size_t max_thr = 0;
+  for (int g = 0; g < F; g++) {
+    std::sort(Th[g].begin(), Th[g].end());
+    Th[g].erase(std::unique(Th[g].begin(), Th[g].end()), Th[g].end());
+    toff[g + 1] = toff[g] + (int64_t)Th[g].size();
+    max_thr = std::max(max_thr, Th[g].size());
+  }
+  const int32_t Sq = (F + 15) / 16 * 16;
+  IjRun R;
+  TRY(ij_prepare(c, f, Gd, w, 2, Sq, F, max_thr <= 65535, N, [&](int g, double thr) {
+    return (int64_t)(std::lower_bound(Th[g].begin(), Th[g].end(), thr) - Th[g].begin());
+  }, R));
+  double* d_out;
+  TRY(ws_typed(c, "ijout", (size_t)N * 3, &d_out));
+  double* d_X;
+  if (R.tiled) {
+    std::vector<double> tv((size_t)std::max<int64_t>(toff[F], 1));
+    for (int g = 0; g < F; g++) std::copy(Th[g].begin(), Th[g].end(), tv.begin() + toff[g]);
+    double* d_T;
+    int64_t* d_toff;
+    TRY(ws_typed(c, "pq_thr", tv.size(), &d_T));
+    TRY(ws_typed(c, "pq_off", toff.size(), &d_toff));
+    TRY(h2d(c, d_T, tv.data(), tv.size()));
+    TRY(h2d(c, d_toff, toff.data(), toff.size()));
+    int64_t batch = std::max<int64_t>(1, std::min<int64_t>(N, ((int64_t)2 << 30) / (8 * (int64_t)F)));
+    if (const char* e = getenv("SBAG_PREDICT_BATCH_ROWS")) batch = std::max<int64_t>(1, std::min<int64_t>(batch, atoll(e)));
+    uint16_t* d_codes;
+    TRY(ws_typed(c, "pX", (size_t)batch * F, &d_X));
+    TRY(ws_typed(c, "pq_codes", (size_t)batch * Sq, &d_codes));
+    for (int64_t r0 = 0; r0 < N; r0 += batch) {
+      const int64_t n = std::min(batch, N - r0);
+      HIP_TRY(hipMemcpyAsync(d_X, X + r0 * F, (size_t)n * F * 8, hipMemcpyHostToDevice, c->stream));
+      launch_quantize(c->stream, d_X, n, F, d_T, d_toff, d_codes, Sq);
+      R.pa.codes = d_codes;
+      R.pa.N = n;
+      R.q.out = d_out + r0 * 3;
+      launch_ij_tiled(c->stream, R.pa, R.q);
+      HIP_TRY(hipGetLastError());
+    }
+  } else {
+    TRY(ws_typed(c, "pX", (size_t)N * F, &d_X));
+    TRY(h2d(c, d_X, X, (size_t)N * F));
+    R.q.out = d_out;
+    TRY(ij_general(c, R, d_X, nullptr, N, F, T));
+  }
+  TRY(d2h(c, out, d_out, (size_t)N * 3));
+  return SBAG_OK;
+}
+
+int sbag_predict_variance_dataset(sbag_ctx* c, const sbag_forest* f, const sbag_dataset* ds, const int64_t* gram,
+                                  double* out) {
+  if (!c || !f || !ds || !gram || !out) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  std::vector<double> Gd;
+  double w = 0.0;
+  TRY(check_variance(f, gram, Gd, &w));
+  TRY(check_quant_dataset(c, f, ds));
+  if (ds->N == 0) return SBAG_OK;
+  HIP_TRY(hipSetDevice(c->device));
+  IjRun R;
+  // TreePoint's `value <= threshold` in the dataset's code space (dict sorted ascending)
+  TRY(ij_prepare(c, f, Gd, w, ds->code_bytes, ds->S, ds->F, ds->code_bytes != 4, ds->N, [&](int g, double thr) {
+    const std::vector<double>& d = ds->dict[g];
+    return (int64_t)(std::upper_bound(d.begin(), d.end(), thr) - d.begin()) - 1;
+  }, R));
+  double* d_out;
+  TRY(ws_typed(c, "ijout", (size_t)ds->N * 3, &d_out));
+  R.q.out = d_out;
+  if (R.tiled) {
+    R.pa.codes = ds->d_codes;
+    R.pa.N = ds->N;
+    launch_ij_tiled(c->stream, R.pa, R.q);
+    HIP_TRY(hipGetLastError());
+  } else {
+    TRY(ij_general(c, R, nullptr, ds, ds->N, ds->F, (int)f->trees.size()));
+  }
+  TRY(d2h(c, out, d_out, (size_t)ds->N * 3));
   return SBAG_OK;
 }
 

@@ -461,6 +461,26 @@ void launch_quant_walk(hipStream_t st, const double* X, const void* codes, int c
                        uint32_t* keys);
 // k_quant_select: a wave per row over keys [L][n]; q.out / q.n_oob are the batch's first row's
 void launch_quant_select(hipStream_t st, const uint32_t* keys, int64_t n, int L, const QuantArgs& q);
+// ---- infinitesimal-jackknife variance (sbag_ij.hip, sbag_ij_plan.h).
+// launch_gram: gram [T][T] int64 (zeroed by the caller) += the lower triangle and diagonal of
+// counts counts' for counts u8 [T][N], readable 32 bytes past its end.  dot false: k_gram_mfma,
+// exact while every byte is < 128, else *flag is set to 1 and gram is to be discarded; dot
+// true: k_gram_dot, any byte.
+void launch_gram(hipStream_t st, const uint8_t* counts, int T, int64_t N, unsigned long long* gram, int* flag,
+                 bool dot);
+struct IjArgs {
+  const double* G;  // [T][T] fp64 copy of the Gram matrix (diagonal and lower triangle read)
+  double w;         // sbag.h's w
+  double tt;        // (double)(T * T)
+  int32_t R;        // k_ij_tiled: rows of a tile (sbag_ij_plan.h)
+  double* out;      // [N][3]: m, v_ij, v_iju
+};
+// k_ij_tiled: k_quant_tiled's geometry at q.R rows a tile over plan_tiled's plan (leaf values in
+// the chunk); LDS = q.R rows + a.chunk_bytes + ij_matrix_lds(a.L, q.R)
+void launch_ij_tiled(hipStream_t st, const PredictArgs& a, const IjArgs& q);
+// k_ij_form: one thread per row over per-tree predictions tp [T][n] (overwritten); q.out is the
+// batch's first row's
+void launch_ij_form(hipStream_t st, double* tp, int64_t n, int T, const IjArgs& q);
 // ---- partial dependence on one feature (sbag_pd.hip): the leaf-occupancy counts
 // cnt[leaf][g] of sbag.h's rule, u64 [leaves of the forest][G], a tree's leaves in node
 // (pre-order) order from leaf_off[t], and their fold into tree_pd / votes / pd.

@@ -1065,6 +1065,51 @@ class BaggingRegressionModel(_BaggingModel):
             X = X[None, :]
         return nat.predict_quantiles(ctx, forest, X, probabilities)
 
+    def bagGram(self, dataset, partition_offsets=None):
+        """int64 [T, T]: the Gram matrix of the model's bag counts over the training rows,
+        G[a][b] = sum_r counts[a][r] * counts[b][r], contracted on the device from the regenerated
+        bags (no count leaves it).  `dataset` and `partition_offsets` as in oobPredictions; only
+        the row count and the partitions are used.  Computed once per model, it serves every
+        predictVariance call."""
+        (lb, le), ds, part, own = self._oob_dataset(dataset, partition_offsets)
+        try:
+            return nat.bag_gram(ds.ctx, replacement=self.get("replacement"), sample_ratio=self.get("sampleRatio"),
+                                seed=self.get("seed"), learner_begin=lb, learner_end=le, num_rows=ds.shape[0],
+                                partition_offsets=part)
+        finally:
+            if own:
+                ds.free()
+
+    def predictVariance(self, dataset, gram, device=0):
+        """(mean, v_ij, v_iju): the bagged prediction and its sampling variance by the
+        infinitesimal jackknife (Wager, Hastie & Efron 2014), plain and with the Monte-Carlo
+        bias correction (which may come out negative); sbag.h states every operation.  `gram`
+        is bagGram's; `dataset` as in transform; a DeviceDataset stays resident."""
+        forest = self.native_forest()
+        if isinstance(dataset, nat.DeviceDataset):
+            out = nat.predict_variance_dataset(dataset.ctx, forest, dataset, gram)
+        else:
+            ctx = nat.default_context(device)
+            X = dataset.features if isinstance(dataset, Frame) else dataset
+            if is_sparse(X):
+                ds = nat.DeviceDataset.from_csr(X, np.zeros(X.shape[0]), ctx)
+                try:
+                    out = nat.predict_variance_dataset(ctx, forest, ds, gram)
+                finally:
+                    ds.free()
+            else:
+                X = np.asarray(X, np.float64)
+                if X.ndim == 1:
+                    X = X[None, :]
+                out = nat.predict_variance(ctx, forest, X, gram)
+        return out[:, 0].copy(), out[:, 1].copy(), out[:, 2].copy()
+
+    def predictStdError(self, dataset, gram, corrected=True, device=0):
+        """The standard error of the bagged prediction: sqrt(max(v, 0)) of predictVariance's
+        v_iju (corrected) or v_ij."""
+        _, v_ij, v_iju = self.predictVariance(dataset, gram, device)
+        return np.sqrt(np.maximum(v_iju if corrected else v_ij, 0.0))
+
     def partialDependence(self, dataset, feature, grid=None, numPoints=32, perTree=False, device=0):
         """(grid, pd): the ensemble's mean prediction over the rows of `dataset` with feature
         `feature` set to each grid value (randomForest's partialPlot), counted on the device in
@@ -1154,6 +1199,12 @@ class BaggingClassificationModel(_BaggingModel):
             nat.SBAG_EINVAL, f"{type(self).__name__} has no quantiles of its votes (a regression model does)")
 
     predictQuantiles = predictInterval = oobQuantiles = _no_spread
+
+    def _no_variance(self, *_a, **_k):
+        raise nat.IllegalArgumentException(
+            nat.SBAG_EINVAL, f"{type(self).__name__} has no variance of its votes (a regression model does)")
+
+    bagGram = predictVariance = predictStdError = _no_variance
 
     @property
     def numClasses(self):
