@@ -218,6 +218,67 @@ int sbag_sample_boosted_stats(sbag_ctx* ctx, sbag_boosted_stats* out);
 int sbag_fit_bag(sbag_ctx* ctx, const sbag_dataset* ds, const sbag_booster_params* p,
                  sbag_forest** out);
 
+/* ---- GBMRegressor's boosting state, resident on the device ------------------------------
+ * GBMRegressor.trainBoosters (ml/regression/GBMRegressor.scala:255-399) keeps, over the rows
+ * of one DataFrame, the current model's BLAS.dot S and what it derives from it every
+ * iteration: on the training rows the pseudo-residuals the next booster is fitted on, on the
+ * validation rows the per-row losses whose sum is the validation error.  A sbag_gbm_state is
+ * bound to one resident dataset and holds, per row, y (the dataset's label column), S (fp64,
+ * +0.0 at first) and `values` (fp64), all on the device; a step is one kernel (k_gbm_step).
+ * With d = y - (S + konst), every operation one IEEE fp64 operation rounded to nearest, none
+ * fused (GBMRegressorParams.lossFunction / gradFunction, GBMRegressor.scala:93-118):
+ *   SBAG_GBM_RESIDUAL  values = -grad(y, S + konst)
+ *     squared   d                                absolute  Math.signum(d): +-0.0 and NaN themselves
+ *     huber     -((-d) / sqrt(1.0 + (d / alpha) * (d / alpha)))
+ *     quantile  (S + konst) > y ? alpha - 1.0 : alpha
+ *   SBAG_GBM_LOSS      values = lossf(y, S + konst)
+ *     squared   (d * d) / 2.0                    absolute  |d|
+ *     huber     (alpha * alpha) * (sqrt(1.0 + (d / alpha) * (d / alpha)) - 1.0)
+ *     quantile  (S + konst) > y ? (alpha - 1.0) * d : alpha * d
+ * (divisions and sqrt correctly rounded, subnormal quotients included).  NaN and infinities
+ * flow through the formulas as they do on the host.
+ *
+ * sbag_gbm_state_create: the state over `ds` (which must outlive it), values computed for
+ *   S = +0.0.  y is read from the dataset at every step: after sbag_dataset_set_labels the next
+ *   step sees the new column.  SBAG_EINVAL: an unknown loss or mode, a dataset on another device than the
+ *   context's; SBAG_EUNSUPPORTED: 2^32 rows or more.
+ * sbag_gbm_fit_next (SBAG_GBM_RESIDUAL states): sbag_fit_booster on the state's dataset with
+ *   the state's values as labels.  Nothing is uploaded and no pass analyses the labels: the
+ *   step that wrote them reduced that analysis alongside.  Validation, error codes (labels
+ *   not finite: SBAG_EUNSUPPORTED, "booster labels must be finite") and the returned one-tree
+ *   forest are sbag_fit_booster's on the same labels, bit for bit.
+ * sbag_gbm_advance: per row, p = the prediction of tree `tree_index` of `f` for the row (the
+ *   tree's subspace maps its feature indices to the dataset's columns; `value <= threshold`
+ *   as sbag_predict_dataset applies it, so `f` may come from another dataset: validation rows),
+ *   S = S + (p * weight) with the product rounded first, then the values from the new S.
+ *   SBAG_EINVAL: a tree index outside the forest, a subspace index past the dataset's features.
+ * sbag_gbm_state_read: host copies of S and of the values, [num_rows] each, either may be NULL.
+ * sbag_gbm_state_step_ms: device time of the state's last step kernel (create's or an advance's;
+ *   0.0 for a state without rows).
+ * sbag_gbm_plan: the rows one workgroup of the step owns (*tile_rows) and whether a tree of
+ *   `num_nodes` nodes is staged into LDS (*tree_in_lds 1) or read from global memory (0).
+ * Every call but sbag_gbm_plan holds the context as the other entries do; a context on another
+ * device than the state's is SBAG_EINVAL.  After any failure the state and the context stay
+ * usable.                                                                                  */
+typedef struct sbag_gbm_state sbag_gbm_state;
+#define SBAG_GBM_SQUARED 0
+#define SBAG_GBM_ABSOLUTE 1
+#define SBAG_GBM_HUBER 2
+#define SBAG_GBM_QUANTILE 3
+#define SBAG_GBM_RESIDUAL 0
+#define SBAG_GBM_LOSS 1
+int sbag_gbm_state_create(sbag_ctx* ctx, const sbag_dataset* ds, int32_t loss, double alpha,
+                          double konst, int32_t mode, sbag_gbm_state** out);
+int sbag_gbm_fit_next(sbag_ctx* ctx, sbag_gbm_state* state, const sbag_booster_params* p,
+                      sbag_forest** out);
+int sbag_gbm_advance(sbag_ctx* ctx, sbag_gbm_state* state, const sbag_forest* f, int32_t tree_index,
+                     double weight);
+int sbag_gbm_state_read(sbag_ctx* ctx, const sbag_gbm_state* state, double* S_out /* host [num_rows] or NULL */,
+                        double* values_out /* host [num_rows] or NULL */);
+int sbag_gbm_state_step_ms(sbag_ctx* ctx, const sbag_gbm_state* state, double* ms_out);
+int sbag_gbm_state_free(sbag_gbm_state* state);
+int sbag_gbm_plan(int32_t num_nodes, int32_t* tile_rows, int32_t* tree_in_lds);
+
 /* ---- forest (BaggingRegressionModel / BaggingClassificationModel fields
  *      `subspaces`, `models`, `numBaseModels`, BaggingRegressor.scala:235-246) */
 typedef struct { /* DecisionTreeModelReadWrite.NodeData, pre-order ids */

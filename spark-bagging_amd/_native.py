@@ -18,6 +18,8 @@ IMPURITY_VARIANCE, IMPURITY_GINI = 0, 1
 AGG_MEAN, AGG_MODE = 0, 1
 OUT_SUM, OUT_VOTES = 2, 3  # device outputs of sbag_predict_dataset_device
 RAW_VOTES, RAW_LEAF = 0, 1  # kinds of sbag_predict_raw: hard / soft voting
+GBM_LOSSES = ("squared", "absolute", "huber", "quantile")  # SBAG_GBM_SQUARED ... _QUANTILE
+GBM_RESIDUAL, GBM_LOSS = 0, 1  # modes of a GbmState: pseudo-residuals / per-row losses
 W_DOT, W_CLASS = 0, 1  # kinds of sbag_predict_weighted: weighted sums / class weights
 PD_MEAN, PD_VOTES = 0, 1  # kinds of sbag_partial_dependence: mean prediction / vote fractions
 COL_F64, COL_F32, COL_U8 = 0, 1, 2  # sbag_dataset_create_columns
@@ -45,6 +47,8 @@ EXPORTED = [
     "sbag_proximity", "sbag_proximity_dataset", "sbag_proximity_moments", "sbag_proximity_moments_dataset",
     "sbag_proximity_topk", "sbag_proximity_topk_dataset",
     "sbag_bag_gram", "sbag_counts_gram", "sbag_predict_variance", "sbag_predict_variance_dataset",
+    "sbag_gbm_state_create", "sbag_gbm_fit_next", "sbag_gbm_advance", "sbag_gbm_state_read",
+    "sbag_gbm_state_step_ms", "sbag_gbm_state_free", "sbag_gbm_plan",
 ]
 
 
@@ -169,6 +173,13 @@ def lib():
             "sbag_sample_boosted": [P, P, i64, P, i32, i64, P],
             "sbag_sample_boosted_stats": [P, ctypes.POINTER(BoostedStats)],
             "sbag_fit_bag": [P, P, ctypes.POINTER(BoosterParams), P],
+            "sbag_gbm_state_create": [P, P, i32, dbl, dbl, i32, P],
+            "sbag_gbm_fit_next": [P, P, ctypes.POINTER(BoosterParams), P],
+            "sbag_gbm_advance": [P, P, P, i32, dbl],
+            "sbag_gbm_state_read": [P, P, P, P],
+            "sbag_gbm_state_step_ms": [P, P, P],
+            "sbag_gbm_state_free": [P],
+            "sbag_gbm_plan": [i32, P, P],
             "sbag_dataset_create_stacked": [P, P, P, P],
             "sbag_predict_stacked": [P, P, P, P, i64, i32, P],
             "sbag_predict_stacked_dataset": [P, P, P, P, P],
@@ -586,6 +597,81 @@ def fit_booster(ctx, dataset, labels, counts, subspace, *, partition_offsets=Non
     check(lib().sbag_fit_booster(ctx.handle, dataset.handle, ptr(labels), ctypes.byref(bp),
                                  ctypes.byref(h)))
     return NativeForest(h, IMPURITY_VARIANCE)
+
+
+def gbm_plan(num_nodes):
+    """(rows one workgroup of the boosting step owns, whether a tree of num_nodes nodes is staged
+    into LDS): sbag_gbm_plan."""
+    tile, lds = ctypes.c_int32(), ctypes.c_int32()
+    check(lib().sbag_gbm_plan(int(num_nodes), ctypes.byref(tile), ctypes.byref(lds)))
+    return tile.value, bool(lds.value)
+
+
+class GbmState:
+    """GBMRegressor's boosting state resident on the device (sbag_gbm_state): per row of
+    `dataset` the model's BLAS.dot S and, by `mode`, the pseudo-residuals -grad(y, S + const)
+    (GBM_RESIDUAL) or the losses lossf(y, S + const) (GBM_LOSS)."""
+
+    def __init__(self, ctx, dataset, loss, alpha, const, mode):
+        self.ctx, self.dataset = ctx, dataset  # (the dataset must outlive the state)
+        self._h = ctypes.c_void_p()
+        check(lib().sbag_gbm_state_create(ctx.handle, dataset.handle, GBM_LOSSES.index(loss), float(alpha),
+                                          float(const), int(mode), ctypes.byref(self._h)))
+
+    @classmethod
+    def create(cls, ctx, dataset, loss, alpha=0.9, const=0.0, mode=GBM_RESIDUAL):
+        return cls(ctx, dataset, loss, alpha, const, mode)
+
+    def fit_next(self, counts, subspace, *, partition_offsets=None, max_depth=5, max_bins=32,
+                 min_instances_per_node=1, min_info_gain=0.0, tree_seed=None):
+        """fit_booster on the state's residuals, which stay on the device (sbag_gbm_fit_next)."""
+        if tree_seed is None:
+            tree_seed = DT_SEED_REGRESSOR
+        counts = np.ascontiguousarray(counts, np.uint8)
+        sub = np.ascontiguousarray(subspace, np.int32)
+        if len(counts) != self.dataset.shape[0]:
+            raise IllegalArgumentException(SBAG_EINVAL, "counts do not match the row count")
+        off = None
+        P = 1
+        if partition_offsets is not None:
+            off = np.ascontiguousarray(partition_offsets, np.int64)
+            P = len(off) - 1
+        bp = BoosterParams(counts.ctypes.data, sub.ctypes.data, len(sub), P,
+                           off.ctypes.data if off is not None else None,
+                           TreeParams(max_depth, max_bins, min_instances_per_node, IMPURITY_VARIANCE,
+                                      float(min_info_gain), int(tree_seed)))
+        h = ctypes.c_void_p()
+        check(lib().sbag_gbm_fit_next(self.ctx.handle, self._h, ctypes.byref(bp), ctypes.byref(h)))
+        return NativeForest(h, IMPURITY_VARIANCE)
+
+    def advance(self, forest, weight, tree_index=0):
+        """S += tree(row) * weight, then the residuals / losses of the new S: one kernel."""
+        check(lib().sbag_gbm_advance(self.ctx.handle, self._h, forest.handle, int(tree_index), float(weight)))
+
+    def read(self, S=True, values=True):
+        """(S, values) as host fp64 arrays (None where not asked for)."""
+        n = self.dataset.shape[0]
+        s = np.zeros(n) if S else None
+        v = np.zeros(n) if values else None
+        check(lib().sbag_gbm_state_read(self.ctx.handle, self._h, ptr(s), ptr(v)))
+        return s, v
+
+    def step_ms(self):
+        """Device time of the last step kernel (create's or an advance's), in ms."""
+        ms = ctypes.c_double()
+        check(lib().sbag_gbm_state_step_ms(self.ctx.handle, self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def free(self):
+        if self._h:
+            lib().sbag_gbm_state_free(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def sample_boosted(ctx, mean, seed, partition_offsets=None):

@@ -33,6 +33,7 @@
 #include "sbag.h"
 #include "sbag_budget.h"
 #include "sbag_fastmath.h"
+#include "sbag_gbm_plan.h"
 #include "sbag_ij_plan.h"
 #include "sbag_internal.h"
 #include "sbag_mfma_plan.h"
@@ -8158,6 +8159,77 @@ int sbag_fit_bag(sbag_ctx* c, const sbag_dataset* ds, const sbag_booster_params*
   return SBAG_OK;
 }
 
+// a booster's label analysis from k_label_stats' / k_gbm_step's six words
+static void label_stats_from_acc(LabelSet& lab, int64_t N, const uint64_t* acc) {
+  auto from_key = [](uint64_t k) {
+    const uint64_t b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
+    double v;
+    std::memcpy(&v, &b, 8);
+    return v;
+  };
+  double amax;
+  std::memcpy(&amax, &acc[5], 8);
+  const bool finite = acc[0] == 0;
+  set_label_stats(lab, N, finite, acc[1] == 0, (int)acc[2], finite ? from_key(acc[3]) : 0.0,
+                  finite ? from_key(acc[4]) : 0.0, amax);
+}
+
+// host-side phase timing of the booster set-up (SBAG_PROFILE_HOST=1 prints it)
+struct BoosterClock {
+  const bool on = getenv("SBAG_PROFILE_HOST") != nullptr;
+  double bt[6] = {0}, b0 = now();
+  static double now() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  }
+  void mark(int k) {
+    const double t = now();
+    bt[k] += t - b0;
+    b0 = t;
+  }
+};
+
+// sbag_fit_booster after its label analysis (shared with sbag_gbm_fit_next): lab.d_y64 holds
+// the finite labels on the device ([N] and one +0.0), lab's stats are set
+static int fit_booster_analyzed(sbag_ctx* c, const sbag_dataset* ds, const sbag_booster_params* bp,
+                                const std::vector<int32_t>& sub, LabelSet& lab, BoosterClock& clk,
+                                sbag_forest** out) {
+  const int64_t N = ds->N;
+  std::vector<int64_t> poff;
+  TRY(check_partitions(bp->num_partitions, bp->partition_offsets, N, poff));
+  HIP_TRY(hipSetDevice(c->device));
+  // the bagging engine with one learner (fit_range): the iteration's bag column and
+  // subspace, its residuals as labels -- screened fp64 splits and row-order sums
+  // (sbag_f64s.hip) for real-valued residuals, the integer engine for dyadic ones
+  {
+    int64_t n_items = 0;
+    for (int64_t r = 0; r < N; r++) n_items += bp->counts[r];
+    if (n_items == 0)
+      return fail(SBAG_EEMPTY, "DecisionTree requires size of input RDD > 0, but was given by "
+                               "empty one.");
+  }
+  clk.mark(1);  // items
+  TRY(ws_typed(c, "bt_labk", (size_t)N, &lab.d_labk));
+  if (lab.label_ok || lab.approx_ok)
+    launch_label_image(c->stream, lab.d_y64, N, lab.label_ok ? lab.shift : lab.ashift, lab.label_ok,
+                       lab.d_labk);
+  else
+    HIP_TRY(hipMemsetAsync(lab.d_labk, 0, (size_t)N * 4, c->stream));
+  HIP_TRY(hipGetLastError());
+  clk.mark(2);  // fixed-point image
+  FitExt ext{bp->counts, sub, &lab};
+  const sbag_fit_params fp = ext_fit_params(bp);
+  sbag_forest* f = nullptr;
+  const int rc = fit_range(c, const_cast<sbag_dataset*>(ds), &fp, &f, &ext);
+  if (rc == kSplitRange) return fail(SBAG_EUNSUPPORTED, "the booster's bins exceed the device budget");
+  TRY(rc);
+  clk.mark(4);  // fit
+  if (clk.on)
+    fprintf(stderr, "[sbag] booster host ms: upload+analysis %.2f items %.2f image %.2f fit %.2f\n",
+            clk.bt[0], clk.bt[1], clk.bt[2], clk.bt[4]);
+  *out = f;
+  return SBAG_OK;
+}
+
 int sbag_fit_booster(sbag_ctx* c, const sbag_dataset* ds, const double* labels,
                      const sbag_booster_params* bp, sbag_forest** out) {
   if (!c || !ds || !labels || !bp || !out || !bp->counts || !bp->subspace)
@@ -8172,17 +8244,7 @@ int sbag_fit_booster(sbag_ctx* c, const sbag_dataset* ds, const double* labels,
   std::vector<int32_t> sub;
   TRY(check_booster_params(ds, bp, sub));
   const int64_t N = ds->N;
-  // host-side phase timing of the booster set-up (SBAG_PROFILE_HOST=1 prints it)
-  const bool bprof = getenv("SBAG_PROFILE_HOST") != nullptr;
-  auto bnow = [] {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  };
-  double bt[6] = {0}, b0 = bnow();
-  auto bmark = [&](int k) {
-    const double t = bnow();
-    bt[k] += t - b0;
-    b0 = t;
-  };
+  BoosterClock clk;
   // the residuals as a label set: uploaded, then analyzed on the device (analyze_labels'
   // quantities, k_label_stats) -- no host pass over the column
   LabelSet lab;
@@ -8199,53 +8261,214 @@ int sbag_fit_booster(sbag_ctx* c, const sbag_dataset* ds, const double* labels,
     HIP_TRY(hipGetLastError());
     uint64_t acc[6];
     TRY(d2h(c, acc, d_acc, 6));
-    auto from_key = [](uint64_t k) {
-      const uint64_t b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-      double v;
-      std::memcpy(&v, &b, 8);
-      return v;
-    };
-    double amax;
-    std::memcpy(&amax, &acc[5], 8);
-    const bool finite = acc[0] == 0;
-    set_label_stats(lab, N, finite, acc[1] == 0, (int)acc[2], finite ? from_key(acc[3]) : 0.0,
-                    finite ? from_key(acc[4]) : 0.0, amax);
+    label_stats_from_acc(lab, N, acc);
   }
   if (!lab.finite) return fail(SBAG_EUNSUPPORTED, "booster labels must be finite");
-  bmark(0);  // upload + analysis
-  std::vector<int64_t> poff;
-  TRY(check_partitions(bp->num_partitions, bp->partition_offsets, N, poff));
-  HIP_TRY(hipSetDevice(c->device));
-  // the bagging engine with one learner (fit_range): the iteration's bag column and
-  // subspace, its residuals as labels -- screened fp64 splits and row-order sums
-  // (sbag_f64s.hip) for real-valued residuals, the integer engine for dyadic ones
-  {
-    int64_t n_items = 0;
-    for (int64_t r = 0; r < N; r++) n_items += bp->counts[r];
-    if (n_items == 0)
-      return fail(SBAG_EEMPTY, "DecisionTree requires size of input RDD > 0, but was given by "
-                               "empty one.");
+  clk.mark(0);  // upload + analysis
+  return fit_booster_analyzed(c, ds, bp, sub, lab, clk, out);
+}
+
+// ====================================================================== resident GBM state
+// GBMRegressor.trainBoosters' per-row state (the model's BLAS.dot S, the pseudo-residuals or
+// the validation losses) on the device between boosters: sbag_gbm.hip, sbag_gbm_plan.h.
+
+}  // extern "C"
+
+struct sbag_gbm_state {
+  sbag_ctx* ctx = nullptr;  // the context whose stream touched the state last
+  const sbag_dataset* ds = nullptr;
+  int device = 0;
+  int loss = 0, mode = 0;
+  double alpha = 0.0, konst = 0.0;
+  double* d_S = nullptr;    // [N]
+  double* d_val = nullptr;  // [N] and one +0.0 (the label of k_f64_hist's padding entries)
+  uint64_t* d_acc = nullptr;  // [6] the values' label analysis (SBAG_GBM_RESIDUAL)
+  hipEvent_t ev[2] = {nullptr, nullptr};  // around the last step's kernel
+  bool stepped = false;
+  ~sbag_gbm_state() {
+    if (!ds) return;
+    (void)hipSetDevice(device);
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    for (void* p : {(void*)d_S, (void*)d_val, (void*)d_acc})
+      if (p) (void)hipFree(p);
   }
-  bmark(1);  // items
-  TRY(ws_typed(c, "bt_labk", (size_t)N, &lab.d_labk));
-  if (lab.label_ok || lab.approx_ok)
-    launch_label_image(c->stream, lab.d_y64, N, lab.label_ok ? lab.shift : lab.ashift, lab.label_ok,
-                       lab.d_labk);
-  else
-    HIP_TRY(hipMemsetAsync(lab.d_labk, 0, (size_t)N * 4, c->stream));
+};
+
+// the entry's context takes the state over: work another context of the device queued on it
+// is waited for first
+static int gbm_enter(sbag_ctx* c, sbag_gbm_state* st) {
+  if (st->device != c->device)
+    return fail(SBAG_EINVAL, "the boosting state lives on device " + std::to_string(st->device) +
+                                 ", the context on device " + std::to_string(c->device));
+  HIP_TRY(hipSetDevice(c->device));
+  if (st->ctx != c) {
+    HIP_TRY(hipStreamSynchronize(st->ctx->stream));
+    st->ctx = c;
+  }
+  return SBAG_OK;
+}
+
+// one k_gbm_step over the state's rows: `nodes` (device, num_nodes of them) or the first step
+static int gbm_step(sbag_ctx* c, sbag_gbm_state* st, const GbmNode* d_nodes, int num_nodes, double weight) {
+  const sbag_dataset* ds = st->ds;
+  if (ds->N == 0) return SBAG_OK;
+  // y: the dataset's label column as it is now (sbag_dataset_set_labels replaces it)
+  double* d_y = nullptr;
+  TRY(f64_device_labels(const_cast<sbag_dataset*>(ds), ds->lab, ds->N, &d_y));
+  if (st->mode == kGbmResidual) {
+    const uint64_t init[6] = {0, 0, 0, ~0ull, 0, 0};
+    TRY(h2d(c, st->d_acc, init, 6));
+  }
+  GbmArgs a{};
+  a.codes = ds->d_codes;
+  a.code_bytes = ds->code_bytes;
+  a.S = ds->S;
+  a.N = ds->N;
+  a.nodes = d_nodes;
+  a.num_nodes = num_nodes;
+  a.init = d_nodes ? 0 : 1;
+  a.y = d_y;
+  a.Sx = st->d_S;
+  a.val = st->d_val;
+  a.acc = st->d_acc;
+  a.weight = weight;
+  a.alpha = st->alpha;
+  a.konst = st->konst;
+  a.loss = st->loss;
+  a.mode = st->mode;
+  HIP_TRY(hipEventRecord(st->ev[0], c->stream));
+  launch_gbm_step(c->stream, a);
   HIP_TRY(hipGetLastError());
-  bmark(2);  // fixed-point image
-  FitExt ext{bp->counts, sub, &lab};
-  const sbag_fit_params fp = ext_fit_params(bp);
-  sbag_forest* f = nullptr;
-  const int rc = fit_range(c, const_cast<sbag_dataset*>(ds), &fp, &f, &ext);
-  if (rc == kSplitRange) return fail(SBAG_EUNSUPPORTED, "the booster's bins exceed the device budget");
-  TRY(rc);
-  bmark(4);  // fit
-  if (bprof)
-    fprintf(stderr, "[sbag] booster host ms: upload+analysis %.2f items %.2f image %.2f fit %.2f\n",
-            bt[0], bt[1], bt[2], bt[4]);
-  *out = f;
+  HIP_TRY(hipEventRecord(st->ev[1], c->stream));
+  st->stepped = true;
+  return SBAG_OK;
+}
+
+extern "C" {
+
+int sbag_gbm_plan(int32_t num_nodes, int32_t* tile_rows, int32_t* tree_in_lds) {
+  if (num_nodes < 0 || !tile_rows || !tree_in_lds) return fail(SBAG_EINVAL, "bad arguments");
+  *tile_rows = kGbmTileRows;
+  *tree_in_lds = gbm_tree_in_lds(num_nodes) ? 1 : 0;
+  return SBAG_OK;
+}
+
+int sbag_gbm_state_create(sbag_ctx* c, const sbag_dataset* ds, int32_t loss, double alpha, double konst,
+                          int32_t mode, sbag_gbm_state** out) {
+  if (!c || !ds || !out) return fail(SBAG_EINVAL, "bad arguments");
+  if (loss < SBAG_GBM_SQUARED || loss > SBAG_GBM_QUANTILE) return fail(SBAG_EINVAL, "unknown GBM loss");
+  if (mode != SBAG_GBM_RESIDUAL && mode != SBAG_GBM_LOSS) return fail(SBAG_EINVAL, "unknown GBM state mode");
+  if (ds->ctx->device != c->device)
+    return fail(SBAG_EINVAL, "dataset lives on device " + std::to_string(ds->ctx->device) +
+                                 ", the context on device " + std::to_string(c->device));
+  CTX_LOCK(c);
+  const int64_t N = ds->N;
+  if (N >= ((int64_t)1 << 32)) return fail(SBAG_EUNSUPPORTED, "boosting state of 2^32 rows or more");
+  HIP_TRY(hipSetDevice(c->device));
+  auto st = std::make_unique<sbag_gbm_state>();
+  st->ctx = c;
+  st->ds = ds;
+  st->device = c->device;
+  st->loss = loss;
+  st->mode = mode;
+  st->alpha = alpha;
+  st->konst = konst;
+  HIP_TRY(hipMalloc(&st->d_S, (size_t)std::max<int64_t>(N, 1) * 8));
+  HIP_TRY(hipMalloc(&st->d_val, (size_t)(N + 1) * 8));
+  HIP_TRY(hipMalloc(&st->d_acc, 6 * 8));
+  HIP_TRY(hipMemset(st->d_val + N, 0, 8));
+  const uint64_t init[6] = {0, 0, 0, ~0ull, 0, 0};  // (no rows: the analysis of no labels)
+  HIP_TRY(hipMemcpy(st->d_acc, init, sizeof(init), hipMemcpyHostToDevice));
+  for (hipEvent_t& e : st->ev) HIP_TRY(hipEventCreate(&e));
+  TRY(gbm_step(c, st.get(), nullptr, 0, 0.0));
+  *out = st.release();
+  return SBAG_OK;
+}
+
+int sbag_gbm_fit_next(sbag_ctx* c, sbag_gbm_state* st, const sbag_booster_params* bp, sbag_forest** out) {
+  if (!c || !st || !bp || !out || !bp->counts || !bp->subspace) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(gbm_enter(c, st));
+  if (st->mode != kGbmResidual) return fail(SBAG_EINVAL, "the boosting state holds losses, not residuals");
+  if (bp->tree.impurity != SBAG_IMPURITY_VARIANCE)
+    return fail(SBAG_EINVAL, "the booster engine fits DecisionTreeRegressor (impurity variance)");
+  const sbag_dataset* ds = st->ds;
+  std::vector<int32_t> sub;
+  TRY(check_booster_params(ds, bp, sub));
+  BoosterClock clk;
+  // the residuals are on the device and the step that wrote them analysed them
+  LabelSet lab;
+  lab.d_y64 = st->d_val;
+  uint64_t acc[6];
+  TRY(d2h(c, acc, st->d_acc, 6));
+  label_stats_from_acc(lab, ds->N, acc);
+  if (!lab.finite) return fail(SBAG_EUNSUPPORTED, "booster labels must be finite");
+  clk.mark(0);
+  return fit_booster_analyzed(c, ds, bp, sub, lab, clk, out);
+}
+
+int sbag_gbm_advance(sbag_ctx* c, sbag_gbm_state* st, const sbag_forest* f, int32_t tree_index, double weight) {
+  if (!c || !st || !f) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  TRY(gbm_enter(c, st));
+  if (tree_index < 0 || (size_t)tree_index >= f->trees.size())
+    return fail(SBAG_EINVAL, "tree index outside the forest");
+  const sbag_dataset* ds = st->ds;
+  const HTree& h = f->trees[tree_index];
+  for (int32_t g : h.sub)
+    if (g >= ds->F) return fail(SBAG_EINVAL, "dataset has fewer features than the model");
+  // the tree as GbmNodes: TreePoint's `value <= threshold` in the dataset's code space
+  std::vector<GbmNode> gn(h.nodes.size());
+  for (size_t i = 0; i < h.nodes.size(); i++) {
+    const sbag_node& n = h.nodes[i];
+    if (n.left < 0) {
+      gn[i] = gbm_leaf(n.prediction);
+      continue;
+    }
+    const int g = h.sub[n.feature];
+    const std::vector<double>& d = ds->dict[g];
+    gn[i] = GbmNode{n.left, n.right, (uint32_t)g, gbm_code_cut(d.data(), d.size(), n.threshold)};
+  }
+  GbmNode* d_nodes;
+  TRY(ws_typed(c, "gbm_nodes", gn.size(), &d_nodes));
+  TRY(h2d(c, d_nodes, gn.data(), gn.size()));
+  return gbm_step(c, st, d_nodes, (int)gn.size(), weight);
+}
+
+int sbag_gbm_state_read(sbag_ctx* c, const sbag_gbm_state* cst, double* S_out, double* values_out) {
+  if (!c || !cst) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  sbag_gbm_state* st = const_cast<sbag_gbm_state*>(cst);
+  TRY(gbm_enter(c, st));
+  const size_t N = (size_t)st->ds->N;
+  if (S_out) TRY(d2h(c, S_out, st->d_S, N));
+  if (values_out) TRY(d2h(c, values_out, st->d_val, N));
+  return SBAG_OK;
+}
+
+int sbag_gbm_state_step_ms(sbag_ctx* c, const sbag_gbm_state* cst, double* ms) {
+  if (!c || !cst || !ms) return fail(SBAG_EINVAL, "bad arguments");
+  CTX_LOCK(c);
+  sbag_gbm_state* st = const_cast<sbag_gbm_state*>(cst);
+  TRY(gbm_enter(c, st));
+  *ms = 0.0;
+  if (!st->stepped) return SBAG_OK;
+  HIP_TRY(hipEventSynchronize(st->ev[1]));
+  float t = 0.f;
+  HIP_TRY(hipEventElapsedTime(&t, st->ev[0], st->ev[1]));
+  *ms = t;
+  return SBAG_OK;
+}
+
+int sbag_gbm_state_free(sbag_gbm_state* st) {
+  if (!st) return SBAG_OK;
+  {
+    CTX_LOCK(st->ctx);
+    (void)hipSetDevice(st->ctx->device);
+    (void)hipStreamSynchronize(st->ctx->stream);  // no step is in flight on its buffers any more
+  }
+  delete st;
   return SBAG_OK;
 }
 

@@ -827,6 +827,27 @@ size_t fb_psum_part_bytes(int64_t nchain, int P, int NB);
 // rint(y 2^shift) (the fp64 screen's image).
 void launch_label_stats(hipStream_t st, const double* y, int64_t N, uint64_t* acc);
 void launch_label_image(hipStream_t st, const double* y, int64_t N, int shift, bool dyadic, int32_t* k);
+// sbag_gbm.hip: one boosting step over a resident dataset's rows (k_gbm_step; the tile, the
+// staged node and the arithmetic: sbag_gbm_plan.h).  Per row: p = the tree's leaf value,
+// S += p * weight (init: S = +0.0 and no tree), then val = -grad(y, S + konst) and the six
+// label-analysis words of launch_label_stats into acc (mode kGbmResidual; acc must hold the
+// initial values), or val = lossf(y, S + konst) (mode kGbmLoss; acc is not touched).
+struct GbmNode;
+struct GbmArgs {
+  const void* codes;     // [N][S] u8 / u16 / u32
+  int32_t code_bytes, S;
+  int64_t N;
+  const GbmNode* nodes;  // the tree, cuts in the dataset's code space
+  int32_t num_nodes;     // 0 with init
+  int32_t init;
+  const double* y;
+  double* Sx;
+  double* val;
+  uint64_t* acc;
+  double weight, alpha, konst;
+  int32_t loss, mode;
+};
+void launch_gbm_step(hipStream_t st, const GbmArgs& a);
 struct F64FinishNode {
   int32_t t, t0;            // task of the chosen feature; task of the first feature with
                             // splits (root: the parent stats), -1 when not needed

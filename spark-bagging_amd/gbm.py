@@ -17,7 +17,8 @@ Per boosting iteration m (GBMRegressor.scala:286-397):
     the bagging sampler) over the training rows, seed = getSeed;
   * subspace = mkSubspace(subspaceRatio, numFeatures, seed_m), seed_0 = getSeed and
     seed_{m+1} = seed_m + iter_m (the recursion's `seed + iter`);
-  * labels = -grad(label, current prediction) in fp64;
+  * labels = -grad(label, current prediction) in fp64 (GBMRegressor: on the device, by the
+    step that last moved the current prediction -- sbag_gbm_state, k_gbm_step);
   * the booster is DecisionTreeRegressor on extractSubBag(bag m): sbag_fit_booster, whose
     split statistics are fp64 sums in Spark's row order (k_bt_hist / k_bt_partition);
   * weight = learningRate (optimizedWeights = false; the breeze LBFGS-B line search of
@@ -356,16 +357,24 @@ class GBMRegressor(_GBMParams):
         L = self.getNumBaseLearners()
         lr = self.getLearningRate()
         lossf = loss_function(self.getLoss(), self.getAlpha())
-        grad = grad_function(self.getLoss(), self.getAlpha())
         ctx = nat.default_context(0)
         ds = nat.DeviceDataset.from_numpy(Xt, yt, ctx)
+        # the loop's per-row state stays on the device (sbag_gbm_state): S and the residuals of
+        # the training rows; S and the losses of the validation rows, resident as a dataset of
+        # their own.  (Validation rows with NaN features, which a dataset refuses, go up as
+        # host rows every iteration and their losses are made here.)
+        state = dsv = vstate = None
+        host_v = len(yv) > 0 and bool(np.isnan(Xv).any())
         try:
             counts = nat.sample(ctx, self.getReplacement(), self.getSampleRatio(), self.getSeed(),
                                 0, L, Nt, tpart if len(tpart) > 2 else None)
             const = 0.0  # findOptimizedConst only with optimizedWeights (refused above)
+            state = nat.GbmState.create(ctx, ds, self.getLoss(), self.getAlpha(), const, nat.GBM_RESIDUAL)
+            if len(yv) and not host_v:
+                dsv = nat.DeviceDataset.from_numpy(Xv, yv, ctx)
+                vstate = nat.GbmState.create(ctx, dsv, self.getLoss(), self.getAlpha(), const, nat.GBM_LOSS)
             weights, subspaces, models = [], [], []
-            S = np.zeros(Nt)            # BLAS.dot of the current model on the training rows
-            SV = np.zeros(len(yv))      # ... on the validation rows
+            SV = np.zeros(len(yv))      # BLAS.dot of the current model on host validation rows
             it, error, num_try, seed = L, DOUBLE_MAX, 0, self.getSeed()
             while it != 0:
                 m = L - it
@@ -374,32 +383,38 @@ class GBMRegressor(_GBMParams):
                     raise nat.IllegalArgumentException(
                         nat.SBAG_EINVAL, "requirement failed: VectorSlicer requires that at least "
                                          "one feature be selected.")
-                residual = -grad(yt, S + const)
-                f = nat.fit_booster(ctx, ds, residual, counts[m], sub,
-                                    partition_offsets=tpart if len(tpart) > 2 else None,
-                                    max_depth=bl.getMaxDepth(), max_bins=bl.getMaxBins(),
-                                    min_instances_per_node=bl.getMinInstancesPerNode(),
-                                    min_info_gain=bl.getMinInfoGain(), tree_seed=bl.getSeed())
+                # labels = -grad(label, S + const), made by the step that last moved S
+                f = state.fit_next(counts[m], sub,
+                                   partition_offsets=tpart if len(tpart) > 2 else None,
+                                   max_depth=bl.getMaxDepth(), max_bins=bl.getMaxBins(),
+                                   min_instances_per_node=bl.getMinInstancesPerNode(),
+                                   min_info_gain=bl.getMinInfoGain(), tree_seed=bl.getSeed())
+                weight = lr * 1.0
                 try:
                     nodes, stats = f.tree(0)
-                    p = nat.predict_dataset(ctx, f, ds, nat.AGG_MEAN)
-                    pv = nat.predict(ctx, f, Xv, nat.AGG_MEAN) if len(yv) else np.zeros(0)
+                    state.advance(f, weight)  # S = S + p * weight, then the next residuals
+                    if vstate is not None:
+                        vstate.advance(f, weight)
+                    elif host_v:
+                        SV = SV + nat.predict(ctx, f, Xv, nat.AGG_MEAN) * weight
                 finally:
                     f.free()
-                weight = lr * 1.0
                 weights.append(weight)
                 subspaces.append(sub)
                 models.append(DecisionTreeModel(nodes, stats, nat.IMPURITY_VARIANCE))
-                S = S + p * weight
-                SV = SV + pv * weight
-                verror = seq_sum(lossf(yv, SV + const)) if len(yv) else DOUBLE_MAX
+                if vstate is not None:  # the per-row losses come down; Spark SQL's sum is made here
+                    verror = seq_sum(vstate.read(S=False)[1])
+                else:
+                    verror = seq_sum(lossf(yv, SV + const)) if host_v else DOUBLE_MAX
                 old_it = it
                 it, error, num_try = terminate(weight, lr, with_validation, error, verror,
                                                self.getTol(), self.getNumRound(), num_try, it)
                 seed = seed + old_it
             keep = len(models) - num_try
         finally:
-            ds.free()
+            for h in (vstate, state, dsv, ds):
+                if h is not None:
+                    h.free()
         model = GBMRegressionModel(weights[:keep], subspaces[:keep], models[:keep], const)
         for k in self._defaults:
             model._values[k] = self.get(k)
