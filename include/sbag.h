@@ -100,6 +100,27 @@ int sbag_dataset_create_csr(sbag_ctx* ctx, int64_t num_rows, int32_t num_feature
 int sbag_dataset_create_columns(sbag_ctx* ctx, int64_t num_rows, int32_t num_features,
                                 int32_t col_type, const void* const* columns, const double* y,
                                 sbag_dataset** out);
+/* Ingest on the device: the same dataset as sbag_dataset_create / _create_columns build from
+   the same arguments, byte for byte (dictionaries, zero codes, code width, row stride, zeroed
+   padding columns and slack, labels), with the dictionaries discovered and the codes written by
+   HIP kernels: the raw values go up in row batches (SBAG_INGEST_BATCH_ROWS lowers the batch),
+   every feature's distinct values are collected in a hash set in HBM, the host sorts at most
+   65 536 values a feature, and a second pass writes the codes once.  A feature with more than
+   65 536 distinct values (u32 codes) takes the host ingest on the same input: the same bytes,
+   and sbag_dataset_ingest_path reports SBAG_INGEST_HOST.  Errors as the host constructors'
+   (a NaN anywhere: SBAG_EINVAL "NaN feature value"); after a failure nothing is returned and
+   every device buffer is freed.                                                           */
+#define SBAG_INGEST_HOST 0
+#define SBAG_INGEST_DEVICE 1
+int sbag_dataset_create_device(sbag_ctx* ctx, int64_t num_rows, int32_t num_features, const double* X,
+                               const double* y, sbag_dataset** out);
+int sbag_dataset_create_columns_device(sbag_ctx* ctx, int64_t num_rows, int32_t num_features,
+                                       int32_t col_type, const void* const* columns, const double* y,
+                                       sbag_dataset** out);
+/* *path = SBAG_INGEST_DEVICE when the codes were produced by the ingest kernels, else
+   SBAG_INGEST_HOST (the host constructors, import, synthetic, stacked, and a _device call that
+   took the host ingest): a fallback is visible.                                            */
+int sbag_dataset_ingest_path(const sbag_dataset* ds, int32_t* path);
 /* Deterministic synthetic data generated directly in HBM (bench workload):
    x[r,f] = splitmix64(seed ^ (r*F+f)) mod 32; num_classes == 0 -> dyadic
    regression label, else a class label in [0, num_classes). */

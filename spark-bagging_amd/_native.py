@@ -23,12 +23,14 @@ GBM_RESIDUAL, GBM_LOSS = 0, 1  # modes of a GbmState: pseudo-residuals / per-row
 W_DOT, W_CLASS = 0, 1  # kinds of sbag_predict_weighted: weighted sums / class weights
 PD_MEAN, PD_VOTES = 0, 1  # kinds of sbag_partial_dependence: mean prediction / vote fractions
 COL_F64, COL_F32, COL_U8 = 0, 1, 2  # sbag_dataset_create_columns
+INGEST_PATHS = ("host", "device")  # SBAG_INGEST_HOST, SBAG_INGEST_DEVICE
 
 # every symbol include/sbag.h declares (checked by tests/test_abi.py)
 EXPORTED = [
     "sbag_device_count", "sbag_ctx_create", "sbag_ctx_destroy", "sbag_last_error", "sbag_version",
     "sbag_sample", "sbag_subspace", "sbag_dataset_create", "sbag_dataset_create_csr",
     "sbag_dataset_create_columns", "sbag_dataset_synthetic",
+    "sbag_dataset_create_device", "sbag_dataset_create_columns_device", "sbag_dataset_ingest_path",
     "sbag_dataset_info", "sbag_dataset_labels", "sbag_dataset_features", "sbag_dataset_free",
     "sbag_dataset_set_labels", "sbag_dataset_layout", "sbag_dataset_export", "sbag_dataset_import",
     "sbag_fit", "sbag_fit_booster", "sbag_forest_num_trees", "sbag_forest_tree_info", "sbag_forest_subspace",
@@ -160,6 +162,9 @@ def lib():
             "sbag_dataset_synthetic": [P, i64, i32, ctypes.c_uint64, i32, P],
             "sbag_dataset_create_csr": [P, i64, i32, P, P, P, P, P],
             "sbag_dataset_create_columns": [P, i64, i32, i32, P, P, P],
+            "sbag_dataset_create_device": [P, i64, i32, P, P, P],
+            "sbag_dataset_create_columns_device": [P, i64, i32, i32, P, P, P],
+            "sbag_dataset_ingest_path": [P, P],
             "sbag_dataset_info": [P, P, P],
             "sbag_dataset_labels": [P, P],
             "sbag_dataset_features": [P, i64, i64, P],
@@ -301,14 +306,22 @@ class DeviceDataset:
         self.ctx, self._h = ctx, handle
         ctx._datasets.add(self)
 
+    @staticmethod
+    def _ingest(ingest):
+        if ingest not in INGEST_PATHS:
+            raise IllegalArgumentException(SBAG_EINVAL, f"ingest must be one of {INGEST_PATHS}, not {ingest!r}")
+        return ingest == "device"
+
     @classmethod
-    def from_numpy(cls, X, y, ctx=None):
+    def from_numpy(cls, X, y, ctx=None, ingest="host"):
+        """Dense rows.  ingest="device": the dictionaries and codes are built by the ingest
+        kernels (sbag_dataset_create_device): the same dataset, byte for byte."""
+        create = lib().sbag_dataset_create_device if cls._ingest(ingest) else lib().sbag_dataset_create
         ctx = ctx or default_context()
         X = np.ascontiguousarray(X, np.float64)
         y = np.ascontiguousarray(y, np.float64)
         h = ctypes.c_void_p()
-        check(lib().sbag_dataset_create(ctx.handle, X.shape[0], X.shape[1], ptr(X), ptr(y),
-                                        ctypes.byref(h)))
+        check(create(ctx.handle, X.shape[0], X.shape[1], ptr(X), ptr(y), ctypes.byref(h)))
         return cls(ctx, h)
 
     @classmethod
@@ -329,9 +342,12 @@ class DeviceDataset:
         return cls(ctx, h)
 
     @classmethod
-    def from_columns(cls, columns, y, ctx=None):
+    def from_columns(cls, columns, y, ctx=None, ingest="host"):
         """Columnar features: a list of F arrays of N values (fp64, fp32 or u8, one dtype),
-        e.g. Arrow / Parquet column chunks (sbag_dataset_create_columns)."""
+        e.g. Arrow / Parquet column chunks (sbag_dataset_create_columns; ingest="device":
+        sbag_dataset_create_columns_device, the columns converted in the kernels)."""
+        create = (lib().sbag_dataset_create_columns_device if cls._ingest(ingest)
+                  else lib().sbag_dataset_create_columns)
         ctx = ctx or default_context()
         kinds = {np.dtype(np.float64): COL_F64, np.dtype(np.float32): COL_F32,
                  np.dtype(np.uint8): COL_U8}
@@ -344,8 +360,7 @@ class DeviceDataset:
             raise IllegalArgumentException(SBAG_EINVAL, "columns and labels differ in length")
         arr = (ctypes.c_void_p * len(cols))(*[c.ctypes.data for c in cols])
         h = ctypes.c_void_p()
-        check(lib().sbag_dataset_create_columns(ctx.handle, len(y), len(cols), kinds[cols[0].dtype],
-                                                arr, ptr(y), ctypes.byref(h)))
+        check(create(ctx.handle, len(y), len(cols), kinds[cols[0].dtype], arr, ptr(y), ctypes.byref(h)))
         return cls(ctx, h)
 
     @classmethod
@@ -365,6 +380,14 @@ class DeviceDataset:
         n, f = ctypes.c_int64(), ctypes.c_int32()
         check(lib().sbag_dataset_info(self._h, ctypes.byref(n), ctypes.byref(f)))
         return n.value, f.value
+
+    @property
+    def ingest_path(self):
+        """"device" when the ingest kernels produced the codes, else "host" (also a
+        device ingest that fell back: sbag_dataset_ingest_path)."""
+        p = ctypes.c_int32()
+        check(lib().sbag_dataset_ingest_path(self._h, ctypes.byref(p)))
+        return INGEST_PATHS[p.value]
 
     def labels(self):
         y = np.zeros(self.shape[0], np.float64)

@@ -35,6 +35,7 @@
 #include "sbag_fastmath.h"
 #include "sbag_gbm_plan.h"
 #include "sbag_ij_plan.h"
+#include "sbag_ingest_plan.h"
 #include "sbag_internal.h"
 #include "sbag_mfma_plan.h"
 #include "sbag_pd_plan.h"
@@ -398,6 +399,7 @@ struct sbag_dataset {
   int64_t N = 0;
   int32_t F = 0, S = 0;     // S: row stride in code elements
   int code_bytes = 1;                     // 4: "wide" (a feature with > 65536 distinct values)
+  int ingest_path = SBAG_INGEST_HOST;     // SBAG_INGEST_DEVICE: the codes are k_ingest_encode's
   void* d_codes = nullptr;
   std::vector<uint32_t> h_codes;          // wide datasets: the codes on the host too [N][S]
   std::vector<std::vector<double>> dict;  // sorted distinct values per feature (-0.0 == 0.0)
@@ -1181,6 +1183,348 @@ int sbag_dataset_create_columns(sbag_ctx* c, int64_t N, int32_t F, int32_t col_t
   src.cols = columns;
   src.col_type = col_type;
   return dataset_from(c, N, F, src, y, out);
+}
+
+// ---- ingest on the device (sbag_ingest.hip, sbag_ingest_plan.h): the same dataset as
+// build_dataset's, byte for byte.  The raw values go up in batches through two pinned staging
+// buffers; pass 1 (k_ingest_distinct) collects every feature's distinct keys in a set in HBM,
+// k_ingest_compact lists them, the host sorts at most 65 536 keys a feature into the dictionaries;
+// pass 2 (k_ingest_encode) writes the codes once, from the raw values kept on the device or, when
+// they do not fit, uploaded again.  Nothing of N elements is sorted and no code crosses PCIe.
+namespace {
+struct DevMem {
+  void* p = nullptr;
+  ~DevMem() {
+    if (p) (void)hipFree(p);
+  }
+};
+struct PinMem {
+  void* p = nullptr;
+  ~PinMem() {
+    if (p) (void)hipHostFree(p);
+  }
+};
+struct StageEvent {
+  hipEvent_t e = nullptr;
+  bool used = false;
+  ~StageEvent() {
+    if (e) (void)hipEventDestroy(e);
+  }
+};
+// SBAG_PROFILE_HOST: device time per stage of a device ingest, from events round every launch
+struct IngestProf {
+  enum { kUpload, kDistinct, kCompact, kRank, kEncode, kStages };
+  bool on = false;
+  hipStream_t st = nullptr;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[kStages];
+  void begin(int s) {
+    if (!on) return;
+    hipEvent_t a = nullptr, b = nullptr;
+    if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) return;
+    (void)hipEventRecord(a, st);
+    ev[s].emplace_back(a, b);
+  }
+  void end(int s) {
+    if (on && !ev[s].empty()) (void)hipEventRecord(ev[s].back().second, st);
+  }
+  double ms(int s) {
+    double t = 0.0;
+    for (auto& p : ev[s]) {
+      float x = 0.f;
+      if (hipEventElapsedTime(&x, p.first, p.second) == hipSuccess) t += x;
+    }
+    return t;
+  }
+  ~IngestProf() {
+    for (auto& v : ev)
+      for (auto& p : v) {
+        (void)hipEventDestroy(p.first);
+        (void)hipEventDestroy(p.second);
+      }
+  }
+};
+constexpr int kIngestTakeHost = INT_MIN;  // ingest_device: the host ingest serves this input
+}  // namespace
+
+static int ingest_device(sbag_ctx* c, int64_t N, int32_t F, const DsSource& src, const double* y,
+                         sbag_dataset** out) {
+  const auto wall0 = std::chrono::steady_clock::now();
+  const int kind = src.kind == 0 ? 0 : src.col_type == SBAG_COL_F64 ? 1 : src.col_type == SBAG_COL_F32 ? 2 : 3;
+  const int elt = kind <= 1 ? 8 : kind == 2 ? 4 : 1;
+  const int32_t S = row_stride(F);
+  if (ingest_encode_rows(S, 2) == 0) return kIngestTakeHost;  // a row of codes does not fit a tile
+  int64_t knob = 0;
+  if (const char* e = getenv("SBAG_INGEST_BATCH_ROWS")) knob = std::max<int64_t>(1, atoll(e));
+  const int64_t batch = ingest_batch_rows(N, F, elt, knob);
+  const int64_t nb = (N + batch - 1) / batch;
+  const size_t stride = ingest_batch_stride(batch, F, elt);
+  const int G = ingest_set_group(F);
+  size_t free_b = 0, total_b = 0;
+  HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+  bool resident = ingest_resident((size_t)nb * stride, (size_t)N * S * 2,
+                                  (size_t)G * (kIngestSetBytes + kIngestRankBytes), free_b, total_b);
+  if (const char* e = getenv("SBAG_INGEST_RESIDENT"))
+    if (atoi(e) == 0) resident = false;
+  int cus = 0;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
+  IngestProf prof;
+  prof.on = getenv("SBAG_PROFILE_HOST") != nullptr;
+  prof.st = c->stream;
+  DevMem raw, sets, ranks;
+  PinMem stage[2];
+  StageEvent sev[2];
+  HIP_TRY(hipMalloc(&raw.p, resident ? (size_t)nb * stride : stride));
+  HIP_TRY(hipMalloc(&sets.p, (size_t)G * kIngestSetBytes));
+  for (int i = 0; i < (nb > 1 ? 2 : 1); i++) {
+    HIP_TRY(hipHostMalloc(&stage[i].p, stride, hipHostMallocDefault));
+    HIP_TRY(hipEventCreateWithFlags(&sev[i].e, hipEventDisableTiming));
+  }
+  const int nw = HostPool::width();
+  int turn = 0;
+  // batch b to the device: staged by the host pool while the other buffer's copy is in flight
+  auto upload = [&](int64_t b) -> int {
+    const int64_t r0 = b * batch, n = std::min(batch, N - r0);
+    const int s = nb > 1 ? turn : 0;
+    turn ^= 1;
+    if (sev[s].used) HIP_TRY(hipEventSynchronize(sev[s].e));
+    uint8_t* dst = (uint8_t*)stage[s].p;
+    const size_t bytes = (size_t)n * F * elt;
+    const int tw = bytes >= ((size_t)1 << 20) ? nw : 1;
+    if (src.kind == 0) {
+      const uint8_t* sp = (const uint8_t*)(src.X + (size_t)r0 * F);
+      c->pool.run(tw, [&](int w) {
+        const size_t lo = bytes * w / tw, hi = bytes * (w + 1) / tw;
+        std::memcpy(dst + lo, sp + lo, hi - lo);
+      });
+    } else {
+      c->pool.run(tw, [&](int w) {
+        for (int f = w; f < F; f += tw)
+          std::memcpy(dst + (size_t)f * n * elt, (const uint8_t*)src.cols[f] + (size_t)r0 * elt, (size_t)n * elt);
+      });
+    }
+    prof.begin(IngestProf::kUpload);
+    HIP_TRY(hipMemcpyAsync((uint8_t*)raw.p + (resident ? (size_t)b * stride : 0), dst, bytes,
+                           hipMemcpyHostToDevice, c->stream));
+    prof.end(IngestProf::kUpload);
+    HIP_TRY(hipEventRecord(sev[s].e, c->stream));
+    sev[s].used = true;
+    return SBAG_OK;
+  };
+  auto batch_raw = [&](int64_t b) { return (const void*)((uint8_t*)raw.p + (resident ? (size_t)b * stride : 0)); };
+
+  // pass 1: the distinct keys, a group of G features' sets at a time
+  uint32_t* d_counts;  // [F] keys inserted, then [F] keys compacted
+  int32_t* d_flags;
+  TRY(ws_typed(c, "ing_counts", (size_t)2 * F, &d_counts));
+  TRY(ws_typed(c, "ing_flags", 2, &d_flags));
+  HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)2 * F * 4, c->stream));
+  HIP_TRY(hipMemsetAsync(d_flags, 0, 8, c->stream));
+  std::vector<uint32_t> counts(F);
+  std::vector<uint64_t> dkeys;  // every feature's keys, sorted below
+  std::vector<int64_t> koff(F + 1, 0);
+  for (int g0 = 0; g0 < F; g0 += G) {
+    const int g1 = std::min(F, g0 + G), ng = g1 - g0;
+    HIP_TRY(hipMemsetAsync(sets.p, 0xFF, (size_t)ng * kIngestSetBytes, c->stream));  // kIngestEmpty
+    for (int64_t b = 0; b < nb; b++) {
+      if (g0 == 0 || !resident) TRY(upload(b));
+      IngestArgs a{};
+      a.raw = batch_raw(b);
+      a.n = std::min(batch, N - b * batch);
+      a.F = F;
+      a.kind = kind;
+      a.f0 = g0;
+      a.f1 = g1;
+      a.sets = (uint64_t*)sets.p;
+      a.counts = d_counts;
+      a.flags = d_flags;
+      a.tiles_per_wg = ingest_distinct_tiles_per_wg(a.n, ng);
+      prof.begin(IngestProf::kDistinct);
+      launch_ingest_distinct(c->stream, a);
+      prof.end(IngestProf::kDistinct);
+      HIP_TRY(hipGetLastError());
+    }
+    int32_t flags[2];
+    TRY(d2h(c, counts.data() + g0, d_counts + g0, (size_t)ng));
+    TRY(d2h(c, flags, d_flags, 2));
+    if (flags[0]) return fail(SBAG_EINVAL, "NaN feature value");
+    if (flags[1]) return kIngestTakeHost;  // more than 65 536 values in a feature: u32 codes
+    std::vector<int64_t> off(ng + 1, 0);
+    for (int i = 0; i < ng; i++) off[i + 1] = off[i] + counts[g0 + i];
+    int64_t* d_off;
+    uint64_t* d_keys;
+    TRY(ws_typed(c, "ing_off", (size_t)ng + 1, &d_off));
+    TRY(ws_typed(c, "ing_keys", (size_t)off[ng], &d_keys));
+    TRY(h2d(c, d_off, off.data(), (size_t)ng + 1));
+    prof.begin(IngestProf::kCompact);
+    launch_ingest_compact(c->stream, (const uint64_t*)sets.p, ng, d_off, d_counts + F + g0, d_keys);
+    prof.end(IngestProf::kCompact);
+    HIP_TRY(hipGetLastError());
+    const size_t base = dkeys.size();
+    dkeys.resize(base + (size_t)off[ng]);
+    TRY(d2h(c, dkeys.data() + base, d_keys, (size_t)off[ng]));
+    for (int i = 0; i < ng; i++) koff[g0 + i + 1] = (int64_t)base + off[i + 1];
+  }
+  if (dkeys.size() > (size_t)INT32_MAX) return kIngestTakeHost;
+
+  // the dictionaries: sorted keys back to values
+  auto ds = std::make_unique<sbag_dataset>();
+  ds->ctx = c;
+  ds->N = N;
+  ds->F = F;
+  ds->S = S;
+  ds->dict.resize(F);
+  ds->zero_code.assign(F, -1);
+  c->pool.run(dkeys.size() >= (1u << 16) ? nw : 1, [&](int w) {
+    const int tw = dkeys.size() >= (1u << 16) ? nw : 1;
+    for (int f = w; f < F; f += tw) {
+      std::sort(dkeys.begin() + koff[f], dkeys.begin() + koff[f + 1]);
+      auto& d = ds->dict[f];
+      d.resize((size_t)(koff[f + 1] - koff[f]));
+      for (size_t i = 0; i < d.size(); i++) d[i] = ingest_value(dkeys[koff[f] + i]);
+      const auto z = std::lower_bound(d.begin(), d.end(), 0.0);
+      if (z != d.end() && *z == 0.0) ds->zero_code[f] = (int)(z - d.begin());
+    }
+  });
+  size_t maxd = 0;
+  for (int f = 0; f < F; f++) maxd = std::max(maxd, ds->dict[f].size());
+  ds->code_bytes = maxd <= 256 ? 1 : 2;
+  const int cb = ds->code_bytes;
+
+  // the encode's plan: LDS dictionaries share the arena (all at once when they fit, else chunk
+  // of features by chunk), the others get a probe table each
+  std::vector<int4> meta(F);
+  std::vector<int32_t> tfeat;
+  std::vector<int2> chunks;
+  int64_t total_pad = 0;
+  for (int f = 0; f < F; f++)
+    if ((int)ds->dict[f].size() <= kIngestLdsDict) total_pad += ingest_pad((int)ds->dict[f].size());
+  const bool one = total_pad <= kIngestArenaKeys;
+  int arena = 1, cur = 0, first = 0;
+  for (int f = 0; f < F; f++) {
+    const int len = (int)ds->dict[f].size();
+    if (len <= kIngestLdsDict) {
+      const int P = ingest_pad(len);
+      if (!one && cur + P > kIngestArenaKeys) {
+        chunks.push_back(make_int2(first, f));
+        first = f;
+        cur = 0;
+      }
+      meta[f] = make_int4((int)koff[f], P, cur, len);
+      cur += P;
+      arena = std::max(arena, cur);
+    } else {
+      meta[f] = make_int4((int)koff[f], 0, (int)tfeat.size(), len);
+      tfeat.push_back(f);
+    }
+  }
+  chunks.push_back(make_int2(first, F));
+  if ((int)tfeat.size() > G) return kIngestTakeHost;  // more probe tables than the set budget holds
+  uint64_t* d_dkeys;
+  int4* d_meta;
+  int2* d_chunks;
+  int32_t* d_tfeat;
+  TRY(ws_typed(c, "ing_dkeys", dkeys.size(), &d_dkeys));
+  TRY(ws_typed(c, "ing_meta", (size_t)F, &d_meta));
+  TRY(ws_typed(c, "ing_chunks", chunks.size(), &d_chunks));
+  TRY(ws_typed(c, "ing_tfeat", tfeat.size(), &d_tfeat));
+  TRY(h2d(c, d_dkeys, dkeys.data(), dkeys.size()));
+  TRY(h2d(c, d_meta, meta.data(), (size_t)F));
+  TRY(h2d(c, d_chunks, chunks.data(), chunks.size()));
+  TRY(h2d(c, d_tfeat, tfeat.data(), tfeat.size()));
+  if (!tfeat.empty()) {
+    HIP_TRY(hipMalloc(&ranks.p, tfeat.size() * kIngestRankBytes));
+    HIP_TRY(hipMemsetAsync(sets.p, 0xFF, tfeat.size() * kIngestSetBytes, c->stream));
+    prof.begin(IngestProf::kRank);
+    launch_ingest_rank(c->stream, d_dkeys, d_meta, d_tfeat, (int)tfeat.size(), (uint64_t*)sets.p,
+                       (uint16_t*)ranks.p);
+    prof.end(IngestProf::kRank);
+    HIP_TRY(hipGetLastError());
+  }
+
+  // pass 2: the codes, written once
+  const size_t row_bytes = (size_t)S * cb;
+  const size_t bytes = (size_t)N * row_bytes;
+  HIP_TRY(hipMalloc(&ds->d_codes, bytes + 256));  // zero slack: k_hist_rl over-reads rows
+  HIP_TRY(hipMemsetAsync((uint8_t*)ds->d_codes + bytes, 0, 256, c->stream));
+  for (int64_t b = 0; b < nb; b++) {
+    if (!resident) TRY(upload(b));
+    IngestEncodeArgs a{};
+    a.raw = batch_raw(b);
+    a.n = std::min(batch, N - b * batch);
+    a.F = F;
+    a.kind = kind;
+    a.S = S;
+    a.R = ingest_encode_rows(S, cb);
+    a.dkeys = d_dkeys;
+    a.meta = d_meta;
+    a.chunks = d_chunks;
+    a.nchunks = (int)chunks.size();
+    a.arena_keys = arena;
+    a.sets = (const uint64_t*)sets.p;
+    a.ranks = (const uint16_t*)ranks.p;
+    a.codes = (uint8_t*)ds->d_codes + (size_t)b * batch * row_bytes;
+    prof.begin(IngestProf::kEncode);
+    launch_ingest_encode(c->stream, a, cb, cus);
+    prof.end(IngestProf::kEncode);
+    HIP_TRY(hipGetLastError());
+  }
+  // the label column, on the host while the encode runs
+  ds->lab.y.assign(y, y + N);
+  analyze_labels(ds.get());
+  TRY(upload_labels(ds.get()));
+  TRY(upload_dict(ds.get()));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  c->pin_used = 0;
+  ds->ingest_path = SBAG_INGEST_DEVICE;
+  if (prof.on) {
+    const double wall = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    fprintf(stderr,
+            "ingest device: rows %lld features %d code_bytes %d batches %lld resident %d upload_ms %.3f "
+            "distinct_ms %.3f compact_ms %.3f rank_ms %.3f encode_ms %.3f total_ms %.3f\n",
+            (long long)N, F, cb, (long long)nb, resident ? 1 : 0, prof.ms(IngestProf::kUpload),
+            prof.ms(IngestProf::kDistinct), prof.ms(IngestProf::kCompact), prof.ms(IngestProf::kRank),
+            prof.ms(IngestProf::kEncode), wall);
+  }
+  ws_trim(c, "ing_keys", (size_t)4 << 20);
+  ws_trim(c, "ing_dkeys", (size_t)4 << 20);
+  *out = ds.release();
+  return SBAG_OK;
+}
+
+static int dataset_from_device(sbag_ctx* c, int64_t N, int32_t F, const DsSource& src, const double* y,
+                               sbag_dataset** out) {
+  if (!c || !out || N < 0 || F <= 0 || (N > 0 && !y)) return fail(SBAG_EINVAL, "bad arguments");
+  if (N == 0) return fail(SBAG_EEMPTY, "ML algorithm was given empty dataset.");
+  if (N >= (int64_t)1 << 32) return fail(SBAG_EUNSUPPORTED, "more than 2^32 rows");
+  TRY(check_source(src, N, F));
+  CTX_LOCK(c);
+  HIP_TRY(hipSetDevice(c->device));
+  const int rc = ingest_device(c, N, F, src, y, out);  // (its transient buffers are freed on return)
+  if (rc == kIngestTakeHost) return build_dataset(c, N, F, src, y, out);
+  return rc;
+}
+
+int sbag_dataset_create_device(sbag_ctx* c, int64_t N, int32_t F, const double* X, const double* y,
+                               sbag_dataset** out) {
+  DsSource src;
+  src.kind = 0;
+  src.X = X;
+  return dataset_from_device(c, N, F, src, y, out);
+}
+
+int sbag_dataset_create_columns_device(sbag_ctx* c, int64_t N, int32_t F, int32_t col_type,
+                                       const void* const* columns, const double* y, sbag_dataset** out) {
+  DsSource src;
+  src.kind = 2;
+  src.cols = columns;
+  src.col_type = col_type;
+  return dataset_from_device(c, N, F, src, y, out);
+}
+
+int sbag_dataset_ingest_path(const sbag_dataset* ds, int32_t* path) {
+  if (!ds || !path) return fail(SBAG_EINVAL, "bad arguments");
+  *path = ds->ingest_path;
+  return SBAG_OK;
 }
 
 int sbag_dataset_synthetic(sbag_ctx* c, int64_t N, int32_t F, uint64_t seed, int32_t num_classes,

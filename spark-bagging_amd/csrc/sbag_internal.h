@@ -890,5 +890,41 @@ void launch_f64_split(hipStream_t st, const F64SplitArgs& a, int nnodes);
 // sbag_dataset_import: *d_bad != 0 when a code is past its dictionary or padding is nonzero
 void launch_check_codes(hipStream_t st, const void* codes, int code_bytes, int64_t N, int32_t S,
                         int32_t F, const int64_t* d_dict_off, int* d_bad);
+// ---- ingest on the device (sbag_ingest.hip, sbag_ingest_plan.h).  A batch of raw values is
+// dense fp64 [n][F] (kind 0) or columns [F][n] of fp64 / fp32 / u8 (kind 1 / 2 / 3), its first
+// byte 16-byte aligned.
+struct IngestArgs {
+  const void* raw;
+  int64_t n;             // rows of the batch
+  int32_t F, kind;
+  int32_t f0, f1;        // the features whose sets are alive
+  uint64_t* sets;        // [f1 - f0][kIngestSlots], kIngestEmpty where free
+  uint32_t* counts;      // [F] keys inserted
+  int32_t* flags;        // [0] a NaN was seen, [1] a feature passed kIngestMaxValues
+  int64_t tiles_per_wg;  // row tiles a workgroup walks
+};
+void launch_ingest_distinct(hipStream_t st, const IngestArgs& a);
+// set y's keys to keys[off[y] .. off[y + 1]) in any order; fill [nsets] zeroed by the caller
+void launch_ingest_compact(hipStream_t st, const uint64_t* sets, int nsets, const int64_t* off, uint32_t* fill,
+                           uint64_t* keys);
+// meta[f]: x first sorted key of feature f in dkeys, w their number, y their number padded to a
+// power of two when k_ingest_encode searches them in LDS (z: offset in the arena), 0 when it
+// probes table z.  Table y (sets / ranks [ntables][kIngestSlots], sets emptied by the caller)
+// is feature feat[y]'s.
+void launch_ingest_rank(hipStream_t st, const uint64_t* dkeys, const int4* meta, const int32_t* feat, int ntables,
+                        uint64_t* sets, uint16_t* ranks);
+struct IngestEncodeArgs {
+  const void* raw;
+  int64_t n;
+  int32_t F, kind, S, R;  // R: rows of a tile (ingest_encode_rows)
+  const uint64_t* dkeys;
+  const int4* meta;
+  const int2* chunks;     // [nchunks] features [x, y) whose LDS dictionaries share the arena
+  int32_t nchunks, arena_keys;
+  const uint64_t* sets;
+  const uint16_t* ranks;
+  void* codes;            // the batch's first row of codes
+};
+void launch_ingest_encode(hipStream_t st, const IngestEncodeArgs& a, int code_bytes, int num_cus);
 
 }  // namespace sbag

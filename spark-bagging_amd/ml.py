@@ -224,10 +224,12 @@ class Frame:
         X, y = load_libsvm(path, sparse=sparse)
         return cls(X, y, partition_offsets=even_partitions(len(y), num_partitions))
 
-    def device_dataset(self, ctx):
+    def device_dataset(self, ctx, ingest="host"):
+        """ingest="device": dense rows are ingested by the device kernels; SparseVector
+        rows keep the host ingest."""
         if is_sparse(self.features):
             return nat.DeviceDataset.from_csr(self.features, self.label, ctx)
-        return nat.DeviceDataset.from_numpy(self.features, self.label, ctx)
+        return nat.DeviceDataset.from_numpy(self.features, self.label, ctx, ingest=ingest)
 
     @property
     def num_rows(self):
